@@ -23,8 +23,24 @@ cpu_baseline: the oracle's C restatement of cpuLS.hpp (oracle/) with its
   oracle keeps a float64 FFT) timed on this host, rank 0 at N=1, on a bounded
   sample of frames of the same shape, OpenMP over frames.
 
-python bench.py [--gpus N] [--steps K] [--warmup W]
+python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 torchrun --nproc-per-node N bench.py --gpus N ...   (one rank per GPU)
+
+A plain run does what the headline needs and no more: synthesise, warm up,
+time --steps steps (the HIP events of the timed steps give roofline and
+stages_ms), write --dump-outputs, print the line.  --full adds, after the
+timed loop, what takes work of its own: the check of the timed output (QPSK
+decisions, timed == warm-up; a failure invalidates the line), the same-box
+HBM probes and the diagnostic build's clock reading, the frequency-domain
+(mode A) measurement and the CPU baseline; --no-cpu, --no-box and --no-mode-a
+drop single parts of it.  Without --full those fields are null.  (--mode
+split and --mode pcie are asked for by name and keep their own checks and
+stage times either way.)
+--dump-outputs DIR writes the last timed step's demodulated symbols to
+DIR/demod.npy (float32, [frame, symbol, subcarrier, re/im]; DIR/demod_rank<r>.npy
+per rank at N > 1): every frame when they fit DUMP_BYTES, else a fixed seeded
+sample of frames, the same for every run of the same arguments -- as are the
+inputs, which are generated from --seed.
 
 `python bench.py --gpus N` (N > 1) without torchrun starts the N ranks
 itself: the launcher process never touches the GPU (it only counts the
@@ -58,6 +74,12 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="frames / freq modes: after the timed loop also check the timed output, probe the "
+                         "box (HBM ceilings, effective clock), measure mode A and time the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's output (all frames, or a fixed seeded sample of them "
+                         "within DUMP_BYTES) to DIR/demod.npy, float32 [frame, symbol, subcarrier, re/im]")
     ap.add_argument("--mode", choices=["frames", "freq", "split", "pcie"], default="frames",
                     help="frames: frame-sharded receiver (configs[3], the headline); freq: the "
                          "same frames in the frequency domain (FFT upstream: LS + MRC alone, "
@@ -91,6 +113,10 @@ def parse():
     ap.add_argument("--pmc", default=os.path.join(ROOT, "profiles", "pmc_traffic.json"),
                     help="PMC traffic summary (profiles/) for roofline.traffic")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.stamps_out and not args.full:
+        ap.error("--stamps-out saves the diagnostic build's stamps, which only a --full run takes")
     split = args.mode == "split"
     args.chunk = args.chunk or (4 if args.mode == "pcie" else 50)
     args.frames = args.frames or (400 if split else 48 if args.mode == "pcie" else 1250)
@@ -316,6 +342,39 @@ def pmc_traffic(path, cfg, build):
     return None, "no profile of this build"
 
 
+DUMP_BYTES = 48 << 20  # --dump-outputs: .npy payload over all ranks (the option's bound is 64 MB)
+
+
+def dump_frames(F, frame_bytes, world=1):
+    """The frames --dump-outputs writes, a function of the shape alone: all F
+    when they fit this rank's share of DUMP_BYTES, else a fixed seeded sample
+    (sorted, always with the first and the last frame)."""
+    import numpy as np
+    n = min(F, DUMP_BYTES // world // frame_bytes)
+    if n < 1:
+        raise SystemExit(f"--dump-outputs: one frame's output ({frame_bytes} B) exceeds the dump budget")
+    if n == F:
+        return np.arange(F)
+    ends = [0, F - 1][:n]
+    inner = np.random.default_rng(20240229).choice(np.arange(1, F - 1), n - len(ends), replace=False)
+    return np.sort(np.concatenate((ends, inner))).astype(np.int64)
+
+
+def dump_outputs(dirname, out, rank=0, world=1):
+    """--dump-outputs: `out` ([F, S-1, K] complex64, device or pinned host) of
+    the last timed step -> DIR/demod.npy (demod_rank<r>.npy at N > 1), float32
+    [frame, symbol, subcarrier, re/im], frames by dump_frames()."""
+    import numpy as np
+    import torch
+    idx = dump_frames(out.shape[0], out[0].numel() * 8, world)
+    sel = out[torch.from_numpy(idx).to(out.device)]
+    arr = torch.view_as_real(sel).cpu().numpy()
+    os.makedirs(dirname, exist_ok=True)
+    path = os.path.join(dirname, "demod.npy" if world == 1 else f"demod_rank{rank}.npy")
+    np.save(path, arr)
+    log(f"[rank {rank}] wrote {path}: {len(idx)} of {out.shape[0]} frames, {arr.nbytes / 1e6:.1f} MB")
+
+
 def visible_gpus():
     """Visible device count without initialising HIP in this process
     (torch.cuda.device_count() does not, on this image)."""
@@ -493,23 +552,28 @@ def main():
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     barrier()
-    errs_warm = int(ofdm.count_symbol_errors(out_w, S, seed=args.seed, frame0=rank * F).item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, rank, world)
 
     ls_ms = None if one else sum(e[0].elapsed_time(e[1]) for e in events) / args.steps
     mrc_all = sorted(e[0 if one else 1].elapsed_time(e[2]) for e in events)
     mrc_ms = sum(mrc_all) / args.steps
     mrc_median = mrc_all[len(mrc_all) // 2]
-    errs = int(ofdm.count_symbol_errors(out, S, seed=args.seed, frame0=rank * F).item())
-    same = bool(torch.equal(out, out_w))
+    errs_warm, errs, same = 0, 0, True  # unchecked without --full (check: null in the line)
+    if args.full:
+        errs_warm = int(ofdm.count_symbol_errors(out_w, S, seed=args.seed, frame0=rank * F).item())
+        errs = int(ofdm.count_symbol_errors(out, S, seed=args.seed, frame0=rank * F).item())
+        same = bool(torch.equal(out, out_w))
     del out_w
     torch.cuda.empty_cache()
 
     # same-box context, after the timed loop (never inside it): the HBM copy /
     # read ceilings of this box, and the effective clock of the timed kernel
     # from its diagnostic build on the same batch
-    box = box_probe(ofdm, torch, dev, stream) if not args.no_box else None
+    probe = args.full and not args.no_box
+    box = box_probe(ofdm, torch, dev, stream) if probe else None
     clock = None
-    if not args.no_box:
+    if probe:
         ws_d = ofdm.workspace(F, S, R, C, dev)
         out_d = ofdm.c64((F, S - 1, K), dev)
 
@@ -602,7 +666,8 @@ def main():
         "per_rank": per_rank,
         "check": {"qpsk_symbol_errors": errs, "timed_equals_warmup": same,
                   "qpsk_symbol_errors_warmup": errs_warm,
-                  "checked_output": "the last timed step's (its buffer NaN-filled before the warm-up)"},
+                  "checked_output": "the last timed step's (its buffer NaN-filled before the warm-up)"}
+        if args.full else None,
         "cpu_baseline": None,
     }
     if failed:  # a broken run never yields a throughput that counts
@@ -613,11 +678,11 @@ def main():
         if world > 1:
             dist.destroy_process_group()
         sys.exit(1)
-    if world == 1 and not freq and not args.no_mode_a:
+    if args.full and world == 1 and not freq and not args.no_mode_a:
         del iq
         torch.cuda.empty_cache()
         result["mode_a"] = mode_a(args, X, ofdm, torch, dev, stream)
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         result["cpu_baseline"] = cpu_baseline(args, X, ofdm, torch, dev)
         result["speedup_vs_cpu_baseline"] = result["value"] / result["cpu_baseline"]["value"]
     if rank == 0:
@@ -715,6 +780,8 @@ def bench_pcie(args, X, dev, world, rank, barrier):
         dist.all_reduce(mx, op=dist.ReduceOp.MAX)
         elapsed = float(mx[0])
     pipe.close()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, rank, world)
     per_step = elapsed / args.steps
     result = {
         "metric": "OFDM symbols/s (LS+MRC) at 1024 subcarriers x 64 ant, PCIe-inclusive "
@@ -792,6 +859,8 @@ def bench_split(args, X, dev, world, rank, barrier):
         elapsed = float(mx[0])
         dist.all_reduce(torch.view_as_real(out))  # the gather: each position is non-zero on one rank only
     torch.cuda.synchronize()
+    if args.dump_outputs and rank == 0:  # the gathered output: one array for the whole job
+        dump_outputs(args.dump_outputs, out)
     errs = int(ofdm.count_symbol_errors(out, S, seed=args.seed).item()) if rank == 0 else 0
     check = {"qpsk_symbol_errors": errs}
     if rank == 0:

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Phases of the one-launch demod's estimator workgroups from the diagnostic
-build's stamps (bench.py --stamps-out X.npy): start -> tables filled (mark
+build's stamps (bench.py --full --stamps-out X.npy): start -> tables filled (mark
 n0) -> first pilot row done (p1) -> all rows (p2) -> |H|^2 stored (p3) ->
 flag published (mark) -> end; and of the first round's receivers: start ->
 estimate seen (mark) -> end.  usage: python scripts/est_phases.py X.npy NLS"""

@@ -7,7 +7,7 @@ set -o pipefail
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 cd "$ROOT"; OUT=gpurun_out/cfg_${1:-final}; mkdir -p $OUT
 run() { name=$1; shift
-  timeout -k 10 300 python -u bench.py --no-cpu --steps 10 "$@" > $OUT/$name.json 2> $OUT/$name.err
+  timeout -k 10 300 python -u bench.py --full --no-cpu --steps 10 "$@" > $OUT/$name.json 2> $OUT/$name.err
   rc=$?; echo "$name rc=$rc"; cat $OUT/$name.json; [ $rc -eq 0 ]; }
 run cfg1_r16 --frames 100 --R 16 && run cfg2_c2048 --frames 1000 --R 64 --C 2048 && \
 run cfg4_split --mode split && run pcie --mode pcie

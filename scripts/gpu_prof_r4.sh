@@ -5,11 +5,11 @@
 # profiled process, so the profiled kernel time is measured inside that run's
 # ms_per_step), then one --pmc pass each for FETCH_SIZE, WRITE_SIZE and
 # GRBM_GUI_ACTIVE + SQ counters (clock and wave-state fractions).
-# usage: bash scripts/gpu_prof_r4.sh <tag> [bench args...]   (default: --gpus 1 --steps 20 --warmup 5)
+# usage: bash scripts/gpu_prof_r4.sh <tag> [bench args...]   (default: --gpus 1 --steps 20 --warmup 5 --full)
 set -o pipefail
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 TAG=${1:-r4}; shift || true
-ARGS="$@"; [ -z "$ARGS" ] && ARGS="--gpus 1 --steps 20 --warmup 5"
+ARGS="$@"; [ -z "$ARGS" ] && ARGS="--gpus 1 --steps 20 --warmup 5 --full"
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp

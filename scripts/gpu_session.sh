@@ -4,7 +4,7 @@
 # usage: bash scripts/gpu_session.sh <tag> step [step ...]
 # steps:
 #   suite      pytest -m gpu (the driver's form)          smoke    __graft_entry__.smoke()
-#   default    bench.py (driver form: 20 steps, 3 warm-up, CPU baseline) + stamps
+#   default    bench.py --full (20 steps, 5 warm-up; checks, box probes, mode A, CPU baseline) + stamps
 #   cfg1       configs[1]: --R 16 --frames 100 --steps 20 --warmup 5 + stamps
 #   cfg1_200   configs[1] at a steady clock: 200 steps after 50 warm-up steps
 #   cfg2       configs[2]: --R 64 --C 2048 --frames 1000 --steps 10
@@ -28,16 +28,16 @@ for st in "$@"; do
            rc=$?; echo "suite rc=$rc"; tail -3 $OUT/pytest.log ;;
     smoke) timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1
            rc=$?; echo "smoke rc=$rc"; tail -2 $OUT/smoke.log ;;
-    default) bench default 600 --gpus 1 --steps 20 --warmup 5 --stamps-out $OUT/stamps_default.npy; rc=$? ;;
-    cfg1) bench cfg1 300 --R 16 --frames 100 --steps 20 --warmup 5 --no-cpu --stamps-out $OUT/stamps_cfg1.npy; rc=$? ;;
-    cfg1_200) bench cfg1_200 300 --R 16 --frames 100 --steps 200 --warmup 50 --no-cpu; rc=$? ;;
-    cfg2) bench cfg2 300 --R 64 --C 2048 --frames 1000 --steps 10 --no-cpu --stamps-out $OUT/stamps_cfg2.npy; rc=$? ;;
-    c4096) bench c4096 300 --R 32 --C 4096 --frames 400 --steps 20 --no-cpu --stamps-out $OUT/stamps_c4096.npy; rc=$? ;;
+    default) bench default 600 --gpus 1 --steps 20 --warmup 5 --full --stamps-out $OUT/stamps_default.npy; rc=$? ;;
+    cfg1) bench cfg1 300 --R 16 --frames 100 --steps 20 --warmup 5 --full --no-cpu --stamps-out $OUT/stamps_cfg1.npy; rc=$? ;;
+    cfg1_200) bench cfg1_200 300 --R 16 --frames 100 --steps 200 --warmup 50 --full --no-cpu; rc=$? ;;
+    cfg2) bench cfg2 300 --R 64 --C 2048 --frames 1000 --steps 10 --full --no-cpu --stamps-out $OUT/stamps_cfg2.npy; rc=$? ;;
+    c4096) bench c4096 300 --R 32 --C 4096 --frames 400 --steps 20 --full --no-cpu --stamps-out $OUT/stamps_c4096.npy; rc=$? ;;
     split) bench split 300 --mode split --no-cpu; rc=$? ;;
-    freq) bench freq 300 --mode freq --no-cpu; rc=$? ;;
+    freq) bench freq 300 --mode freq --full --no-cpu; rc=$? ;;
     prof_default) timeout -k 10 1000 bash scripts/gpu_prof_r4.sh ${TAG}_default > $OUT/prof_default.log 2>&1; rc=$?; echo "prof_default rc=$rc"; tail -3 $OUT/prof_default.log ;;
-    prof_cfg1) timeout -k 10 600 bash scripts/gpu_prof_r4.sh ${TAG}_cfg1 --gpus 1 --steps 20 --warmup 5 --R 16 --frames 100 > $OUT/prof_cfg1.log 2>&1; rc=$?; echo "prof_cfg1 rc=$rc"; tail -3 $OUT/prof_cfg1.log ;;
-    prof_c4096) timeout -k 10 800 bash scripts/gpu_prof_r4.sh ${TAG}_c4096 --gpus 1 --steps 20 --warmup 5 --R 32 --C 4096 --frames 400 > $OUT/prof_c4096.log 2>&1; rc=$?; echo "prof_c4096 rc=$rc"; tail -3 $OUT/prof_c4096.log ;;
+    prof_cfg1) timeout -k 10 600 bash scripts/gpu_prof_r4.sh ${TAG}_cfg1 --gpus 1 --steps 20 --warmup 5 --full --R 16 --frames 100 > $OUT/prof_cfg1.log 2>&1; rc=$?; echo "prof_cfg1 rc=$rc"; tail -3 $OUT/prof_cfg1.log ;;
+    prof_c4096) timeout -k 10 800 bash scripts/gpu_prof_r4.sh ${TAG}_c4096 --gpus 1 --steps 20 --warmup 5 --full --R 32 --C 4096 --frames 400 > $OUT/prof_c4096.log 2>&1; rc=$?; echo "prof_c4096 rc=$rc"; tail -3 $OUT/prof_c4096.log ;;
     clk_cfg1) for g in 0 9; do timeout -k 10 200 python -u scripts/dispatch_clock.py --R 16 --frames 100 --steps 20 --warmup 5 --gap-ms $g --tag cfg1_gap$g >> $OUT/clk_cfg1.jsonl 2>> $OUT/clk.err || { rc=1; break; }; done
               timeout -k 10 200 python -u scripts/dispatch_clock.py --R 16 --frames 100 --steps 200 --warmup 5 --tag cfg1_200 >> $OUT/clk_cfg1.jsonl 2>> $OUT/clk.err; rc=$?
               echo "clk_cfg1 rc=$rc"; grep summary $OUT/clk_cfg1.jsonl ;;

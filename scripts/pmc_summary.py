@@ -98,7 +98,7 @@ def main():
         json.dump(out, fp, indent=1)
 
     md = [f"# Profile {tag}", "",
-          f"Command: `rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 5 --warmup 1 --no-cpu` "
+          f"Command: `rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 5 --warmup 1 --full --no-cpu` "
           f"(then one `--pmc FETCH_SIZE` and one `--pmc WRITE_SIZE` pass, `--steps 2`), "
           f"config {json.dumps(out['config'])}.", "",
           "## Kernel time (rocprofv3 --stats)", "",

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Phases of the one-launch demod's receiver workgroups from the diagnostic
-build's stamps (bench.py --stamps-out X.npy; frame_td.hip k_demod_td1024:
+build's stamps (bench.py --full --stamps-out X.npy; frame_td.hip k_demod_td1024:
 MARKN(0) ticket taken, MARKN(1) tables filled and row 0's DMA issued, MARK
 estimate seen, MARKN(2) rows done (whole blocks only; half units return
 before it), end after the epilogue).  usage: python scripts/rx_phases.py X.npy NLS

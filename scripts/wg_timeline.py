@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Workgroup timeline of one launch from the diagnostic build's stamps
-(bench.py --stamps-out X.npy; csrc/diag.hpp: per workgroup rt_start, rt_mark,
+(bench.py --full --stamps-out X.npy; csrc/diag.hpp: per workgroup rt_start, rt_mark,
 rt_end in 100 MHz ticks, mt_start / mt_end shader clock, hw_id, xcc_id,
 block).
 

@@ -181,7 +181,7 @@ def test_frame_sharded_bench_two_ranks(tmp_path):
     env = dict(os.environ, OFDM_BENCH_SHARE_GPU="1", OFDM_BENCH_BACKEND="gloo")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"),
-                        "--gpus", "2", "--frames", "24", "--steps", "2", "--warmup", "1", "--no-cpu"],
+                        "--gpus", "2", "--frames", "24", "--steps", "2", "--warmup", "1", "--full", "--no-cpu"],
                        capture_output=True, text=True, timeout=180, env=env, cwd=str(tmp_path))
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -244,7 +244,8 @@ def test_bench_gpus2_launches_two_ranks_itself():
     """`python bench.py --gpus 2` with no torchrun starts its two ranks
     itself (here sharing cuda:0 over gloo): n_gpus = 2, both ranks' frames
     counted, the timed output identical to the warm-up's."""
-    line = _line(_bench(["--gpus", "2", "--frames", "24", "--steps", "2", "--warmup", "1", "--no-cpu"], True))
+    line = _line(_bench(["--gpus", "2", "--frames", "24", "--steps", "2", "--warmup", "1", "--full", "--no-cpu"],
+                        True))
     assert line["n_gpus"] == 2 and line["config"]["global_data_symbols"] == 2 * 24 * 100
     assert line["check"]["qpsk_symbol_errors"] == 0 and line["check"]["timed_equals_warmup"] is True
     # VERDICT r4 item 4: per-rank spread of the step and kernel times

@@ -117,3 +117,48 @@ def test_pmc_traffic_only_for_the_profiled_build(tmp_path):
     assert '"build_id": build' in _src("bench.py")
     assert '"build_id": bench.get("build_id")' in _src("scripts/pmc_summary.py")
     assert '"build_id": traced.get("build_id")' in _src("scripts/prof_summary_r4.py")
+
+
+def _bench_mod():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+@pytest.mark.parametrize("F,S,C,world", [(1250, 101, 1024, 1), (1250, 101, 1024, 8), (400, 101, 4096, 1),
+                                         (6, 4, 1024, 1), (2, 101, 1024, 32)])
+def test_dump_frames_fixed_sample_within_budget(F, S, C, world):
+    """--dump-outputs: the dumped frames depend on the shape alone (two runs
+    and two builds dump the same ones), are sorted and distinct, hold the
+    first frame (and the last when more than one fits), are all the frames
+    when those fit, and over all ranks stay within 64 MB."""
+    import numpy as np
+    bench = _bench_mod()
+    fb = (S - 1) * (C - 1) * 8
+    idx = bench.dump_frames(F, fb, world)
+    assert np.array_equal(idx, bench.dump_frames(F, fb, world))
+    assert len(idx) >= 1 and idx[0] == 0 and np.all(np.diff(idx) > 0) and idx[-1] <= F - 1
+    assert len(idx) * fb * world <= bench.DUMP_BYTES <= 64e6
+    if F * fb * world <= bench.DUMP_BYTES:
+        assert len(idx) == F
+    else:
+        assert len(idx) == bench.DUMP_BYTES // world // fb  # the budget is used, not a token sample
+    if len(idx) > 1:
+        assert idx[-1] == F - 1
+
+
+def test_dump_outputs_writes_float32_pairs(tmp_path):
+    """dump_outputs on a host tensor: DIR/demod.npy is float32 [frame, symbol,
+    subcarrier, re/im] of the complex output, bit for bit."""
+    import numpy as np
+    import torch
+    bench = _bench_mod()
+    out = torch.randn(3, 4, 7, dtype=torch.complex64, generator=torch.Generator().manual_seed(1))
+    bench.dump_outputs(str(tmp_path / "d"), out)
+    got = np.load(tmp_path / "d" / "demod.npy")
+    assert got.dtype == np.float32 and got.shape == (3, 4, 7, 2)
+    assert np.array_equal(got[..., 0] + 1j * got[..., 1], out.numpy())
+    bench.dump_outputs(str(tmp_path / "d"), out, rank=1, world=2)
+    assert np.array_equal(np.load(tmp_path / "d" / "demod_rank1.npy"), got)
