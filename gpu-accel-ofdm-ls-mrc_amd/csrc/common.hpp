@@ -94,6 +94,64 @@ __device__ __forceinline__ void fft_reg(float2 (&a)[N]) {
     }
 }
 
+// Forward 16-point FFT, fft_reg<16, false>'s structure and order, with every
+// twiddled butterfly in 6 FMAs instead of 8 operations (complex multiply in
+// mul, fma, mul, fma, then 4 add/sub): the larger of |c|, |s| of the twiddle
+// w = (c, s) is factored out (Linzer-Feig),
+//   |c| >= |s|, t = s/c:  p = (v.x - t v.y, v.y + t v.x),  u +- c p
+//   otherwise,  t = c/s:  p = (t v.x - v.y, t v.y + v.x),  u +- s p
+// with t and the factor compile-time constants from kTw.  For the W8-type
+// twiddles (|c| = |s|, t = +-1) p is a plain add/sub.  10 of the 32
+// butterflies are twiddled: 60 operations instead of 80, each result with
+// fewer roundings than fft_reg's (one per FMA; the ratio t carries the one
+// extra rounding of the constant).  The C = 1024 receivers' rows (the
+// one-launch and two-launch kernels alike: they must agree) use this one;
+// every other caller keeps fft_reg.
+__device__ __forceinline__ void fft16_fma(float2 (&a)[16]) {
+    constexpr int N = 16;
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        const int j = bitrev<N>(i);
+        if (i < j) { float2 t = a[i]; a[i] = a[j]; a[j] = t; }
+    }
+#pragma unroll
+    for (int len = 2; len <= N; len <<= 1) {
+        const int half = len >> 1;
+#pragma unroll
+        for (int i = 0; i < N; i += len) {
+#pragma unroll
+            for (int k = 0; k < half; ++k) {
+                const float2 u = a[i + k], v = a[i + k + half];
+                if (k == 0 || 4 * k == len) {
+                    const float2 p = k == 0 ? v : cmul_mi<false>(v);
+                    a[i + k] = cadd(u, p);
+                    a[i + k + half] = csub(u, p);
+                    continue;
+                }
+                const int idx = k * (OFDM_TW_N / len);
+                const float c = kTw.v[2 * idx], s = kTw.v[2 * idx + 1];
+                const float ac = c < 0.f ? -c : c, as = s < 0.f ? -s : s;
+                float2 p;
+                float m;
+                if (ac == as) {  // t = s/c = +-1
+                    p = c == s ? float2{v.x - v.y, v.y + v.x} : float2{v.x + v.y, v.y - v.x};
+                    m = c;
+                } else if (ac > as) {
+                    const float t = s / c;
+                    p = float2{__builtin_fmaf(-t, v.y, v.x), __builtin_fmaf(t, v.x, v.y)};
+                    m = c;
+                } else {
+                    const float t = c / s;
+                    p = float2{__builtin_fmaf(t, v.x, -v.y), __builtin_fmaf(t, v.y, v.x)};
+                    m = s;
+                }
+                a[i + k] = float2{__builtin_fmaf(m, p.x, u.x), __builtin_fmaf(m, p.y, u.y)};
+                a[i + k + half] = float2{__builtin_fmaf(-m, p.x, u.x), __builtin_fmaf(-m, p.y, u.y)};
+            }
+        }
+    }
+}
+
 // --------------------------------------------------------------------------
 // Block-cooperative Stockham autosort FFT in LDS (radix-4 stages, one final
 // radix-2 stage when log2(C) is odd).  Input in `a`, scratch `b`; returns the

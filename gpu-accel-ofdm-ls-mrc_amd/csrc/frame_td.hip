@@ -120,33 +120,54 @@ __global__ void __launch_bounds__(64 * NW) k_ls_td1024(const float2 *__restrict_
 // read with per-lane affine addresses and no bank conflicts.
 // ---------------------------------------------------------------------------
 
+// The row transform of every C = 1024 kernel in this file (estimator
+// workgroups, the bounded-wait fallback, the shared and non-shared row loops,
+// split_unit, the two-launch pair): plain f32, table twiddles, fused-FMA
+// 16-point transforms (fft16_fma, common.hpp).
+__device__ __forceinline__ void fft_a(float2 (&a)[16], int t, float2 *T, const float2 *tw1) {
+    hlds::row_fft_a<0, false, true>(a, t, T, tw1);
+}
+__device__ __forceinline__ void fft_b(int t, float2 *T, const float2 *tw2, float2 (&x)[16]) {
+    hlds::row_fft_b<0, false, true>(t, T, tw2, x);
+}
+// acc += x * v, matrixMultThenSum (cpuLS.hpp:203-204) with the antennas in
+// order, as two chained FMAs per component (64 VALU per row for the 16 bins;
+// the reference's rounding order, products summed first and then added,
+// compiles to mul + fma + add: 96).
+__device__ __forceinline__ void mac(float2 &acc, float2 x, float vx, float vy) {
+    acc.x = __builtin_fmaf(-x.y, vy, __builtin_fmaf(x.x, vx, acc.x));
+    acc.y = __builtin_fmaf(x.y, vx, __builtin_fmaf(x.x, vy, acc.y));
+}
+
 
 // One antenna row of the prefetching loop: a[] holds this row on entry and
-// the next row (`next`, when PREF) on exit.
+// the next row (`next`, when PREF) on exit.  The thread's 16 B of the Hc row
+// are a buffer load -- hc: the frame's estimates, hoff: the byte offset of
+// (row, this wave's 1 KiB), in SGPRs; the lane's offset is formed here -- so
+// that no per-thread 64-bit pointer stays live across the loop.
+typedef int v4i_t __attribute__((ext_vector_type(4)));
 template <bool PREF>
-__device__ __forceinline__ void hlds_row_pf(const float2 *next, const float4 *hrow, int t, float2 (&a)[16],
+__device__ __forceinline__ void hlds_row_pf(const float2 *next, __amdgpu_buffer_rsrc_t hc, int hoff, int t,
+                                            float2 (&a)[16],
                                             float2 *T, const float2 *tw1, const float2 *tw2,
                                             const float4 *lo, const float4 *hi, float4 *mine,
                                             float2 (&acc)[16]) {
     using namespace hlds;
     float2 x[16];
-    row_fft_a(a, t, T, tw1);
+    fft_a(a, t, T, tw1);
     // a row is 512 float4: each of the 512 threads moves 16 B
-    const float4 hreg = hrow[threadIdx.x];
+    const float4 hreg = __builtin_bit_cast(float4, (v4i_t)__builtin_amdgcn_raw_buffer_load_b128(hc, t * 16, hoff, 0));
     __builtin_amdgcn_sched_barrier(0);
     if (PREF) row_load<true>(next, t, a);
-    row_fft_b(t, T, tw2, x);
+    fft_b(t, T, tw2, x);
     lds_barrier();  // every wave is done with the previous Hc row
     *mine = hreg;
     lds_barrier();
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
         const float4 v = i < 4 ? lo[i * 64] : hi[(i - 4) * TS];  // 2 images = TS float4s
-        // matrixMultThenSum (cpuLS.hpp:203-204), antennas in order
-        acc[2 * i].x = acc[2 * i].x + (x[2 * i].x * v.x - x[2 * i].y * v.y);
-        acc[2 * i].y = acc[2 * i].y + (x[2 * i].x * v.y + x[2 * i].y * v.x);
-        acc[2 * i + 1].x = acc[2 * i + 1].x + (x[2 * i + 1].x * v.z - x[2 * i + 1].y * v.w);
-        acc[2 * i + 1].y = acc[2 * i + 1].y + (x[2 * i + 1].x * v.w + x[2 * i + 1].y * v.z);
+        mac(acc[2 * i], x[2 * i], v.x, v.y);
+        mac(acc[2 * i + 1], x[2 * i + 1], v.z, v.w);
     }
 }
 
@@ -188,17 +209,21 @@ __device__ __forceinline__ void hlds_rows(const float2 *sym, int Cp, int R, cons
     for (int k = 0; k < 16; ++k) acc[k] = float2{0.f, 0.f};
     if constexpr (SHARED) {
         float2 a[16];
-        row0<R0>(sym, t, T, a);
-        const float4 *lo = hfree + t;
-        const float4 *hi = hslot(T0, hfree, 256 + t);
+        const int tl = lane_here();  // the caller's t need not stay live up to here
+        row0<R0>(sym, tl, T, a);
+        const float4 *lo = hfree + tl;
+        const float4 *hi = hslot(T0, hfree, 256 + tl);
         float4 *mine = hslot(T0, hfree, threadIdx.x);
+        // the frame's R rows of 8 KiB; a row is 512 float4, 64 per wave
+        const __amdgpu_buffer_rsrc_t hc =
+            __builtin_amdgcn_make_buffer_rsrc(const_cast<float4 *>(Hf), (short)0, R * (C * 8), 0x00020000);
+        const int hw = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) * 1024;
         // the last row is peeled so that the prefetch is unconditional: the
         // wait for the Hc word before the exchange is then vmcnt(16), not 0
         for (int r = 0; r + 1 < R; ++r)
-            hlds_row_pf<true>(sym + (long long)(r + 1) * Cp, Hf + (long long)r * (C / 2), lane_here(), a, T, tw1,
-                                   tw2, lo, hi, mine, acc);
-        hlds_row_pf<false>(sym, Hf + (long long)(R - 1) * (C / 2), lane_here(), a, T, tw1, tw2, lo, hi, mine,
-                           acc);
+            hlds_row_pf<true>(sym + (long long)(r + 1) * Cp, hc, r * (C * 8) + hw, lane_here(), a, T, tw1, tw2, lo,
+                              hi, mine, acc);
+        hlds_row_pf<false>(sym, hc, (R - 1) * (C * 8) + hw, lane_here(), a, T, tw1, tw2, lo, hi, mine, acc);
     } else {
         for (int r = 0; r < R; ++r) {
             float2 a[16], x[16], h[16];
@@ -206,15 +231,12 @@ __device__ __forceinline__ void hlds_rows(const float2 *sym, int Cp, int R, cons
                 row0<R0>(sym, t, T, a);
             else
                 row_load<true>(sym + (long long)r * Cp, t, a);
-            row_fft_a(a, t, T, tw1);
-            row_fft_b(t, T, tw2, x);
+            fft_a(a, t, T, tw1);
+            fft_b(t, T, tw2, x);
             __builtin_amdgcn_sched_barrier(0);
             hc_load(Hf + (long long)r * (C / 2), t, h);
 #pragma unroll
-            for (int k = 0; k < 16; ++k) {
-                acc[k].x = acc[k].x + (x[k].x * h[k].x - x[k].y * h[k].y);
-                acc[k].y = acc[k].y + (x[k].x * h[k].y + x[k].y * h[k].x);
-            }
+            for (int k = 0; k < 16; ++k) mac(acc[k], x[k], h[k].x, h[k].y);
         }
     }
 }
@@ -294,7 +316,7 @@ k_mrc_td1024_hlds(const float2 *__restrict__ iq, int S, int R, int prefix, const
     const long long q = store ? qw : nq - 1;
     // the workgroup's Hc rows come from the frame of its first symbol; a
     // workgroup straddling two frames falls back to per-wave L2 loads
-    const long long f = q / nsym;
+    const long long f = uniform64(q / nsym);  // wave-uniform: SGPRs across the row loop
     const long long f0 = (lb * HW) / nsym;
     const long long fl = ((lb * HW + HW - 1 < nq ? lb * HW + HW - 1 : nq - 1)) / nsym;
     const int s = 1 + (int)(q % nsym);
@@ -312,7 +334,7 @@ k_mrc_td1024_hlds(const float2 *__restrict__ iq, int S, int R, int prefix, const
         hlds_rows<false, R0>(sym, Cp, R, reinterpret_cast<const float4 *>(Hc + f * (long long)R * C), t, T,
                                 tw1, tw2, T0, hfree, acc);
     if (!store) return;
-    hlds_epilogue(acc, P, f, q, t, T, out, mode);
+    hlds_epilogue(acc, P, f, q, lane_here(), T, out, mode);
 }
 
 
@@ -361,8 +383,8 @@ __device__ __forceinline__ void hlds_ls_frame(const float2 *__restrict__ iq, int
         float2 a[16], x[16];
         const int tl = lane_here();
         row_load<true>(pilot + (long long)r * Cp, tl, a);
-        row_fft_a(a, tl, T, tw1);
-        row_fft_b(tl, T, tw2, x);
+        fft_a(a, tl, T, tw1);
+        fft_b(tl, T, tw2, x);
 #pragma unroll
         for (int k = 0; k < 16; ++k) {
             float2 h = ls_conj(x[k], xp[k]);  // divideOneRow + conj (cpuLS.hpp:233-244)
@@ -421,15 +443,12 @@ __device__ __forceinline__ void split_unit(const float2 *__restrict__ iq, int S,
     for (int r = hh ? R0 : 0; r < r1; ++r) {
         float2 a[16], x[16], h[16];
         row_load<true>(sym + (long long)r * Cp, t, a);
-        hlds::row_fft_a(a, t, T, tw1);
-        hlds::row_fft_b(t, T, tw2, x);
+        fft_a(a, t, T, tw1);
+        fft_b(t, T, tw2, x);
         __builtin_amdgcn_sched_barrier(0);
         hc_load(Hf + (long long)r * (C / 2), t, h);
 #pragma unroll
-        for (int k = 0; k < 16; ++k) {  // matrixMultThenSum (cpuLS.hpp:203-204), antennas in order per half
-            acc[k].x = acc[k].x + (x[k].x * h[k].x - x[k].y * h[k].y);
-            acc[k].y = acc[k].y + (x[k].x * h[k].y + x[k].y * h[k].x);
-        }
+        for (int k = 0; k < 16; ++k) mac(acc[k], x[k], h[k].x, h[k].y);  // antennas in order per half
     }
     if (hh) {
 #pragma unroll
@@ -533,7 +552,7 @@ k_demod_td1024(const float2 *__restrict__ iq, int S, int R, int prefix, const fl
         hlds_ls_frame(iq, S, R, prefix, X, Hc, P, ff, w, t, T, T0, tw1, tw2, OFDM_DIAG_ARG);
     if (estimator) {
         OFDM_DIAG_MARK()
-        publish_flag(flags + e0, epoch);
+        publish_flag(flags + e0, epoch, w == 0 && lane_here() == 0);
         OFDM_DIAG_END_SLOT(td1024, epoch);
         return;
     }

@@ -164,10 +164,13 @@ __device__ __forceinline__ void quad_dft(float2 (&x)[16], int qa) {
 
 // Forward 1024-point FFT of the row held in a[] (see header); T is this
 // wave's transpose region.  On return x[k'] = X[b0 + 16 k'],
-// b0 = (t >> 2) + 256 c(t & 3).
+// b0 = (t >> 2) + 256 c(t & 3).  The 16-point transforms are fft16_fma, as in
+// the C = 1024 kernels' hlds::row_fft_a / row_fft_b<0, false, true>: the
+// two-launch estimator (k_ls_td1024) and the one-launch kernel's compute the
+// same estimate.
 __device__ __forceinline__ void row_fft(float2 (&a)[16], int t, float2 *T, const float2 *tw,
                                         float2 (&x)[16]) {
-    fft_reg<16, false>(a);
+    fft16_fma(a);
 #pragma unroll
     for (int k2 = 1; k2 < 16; ++k2) a[k2] = cmul(a[k2], tw[t * TW1P + k2]);
 #pragma unroll
@@ -177,7 +180,7 @@ __device__ __forceinline__ void row_fft(float2 (&a)[16], int t, float2 *T, const
 #pragma unroll
     for (int l = 0; l < 16; ++l) x[l] = T[q * TP + qa + 4 * l];
     wave_lds_sync();
-    fft_reg<16, false>(x);
+    fft16_fma(x);
     const float2 *tw2 = tw + TW1BUF + qa * TW2P;
     const float g = quad_g(qa);
     x[0] = float2{g * x[0].x, g * x[0].y};
@@ -243,11 +246,13 @@ __device__ __forceinline__ void store4_wt(float *p, float v) {
 }
 
 // producer, every thread of the workgroup: its stores drained, barrier, one
-// lane publishes
-__device__ __forceinline__ void publish_flag(unsigned long long *flag, unsigned long long epoch) {
+// lane publishes.  one: true in exactly one thread (a kernel short of
+// registers forms it from lane_here(), so that threadIdx.x need not stay live
+// up to here).
+__device__ __forceinline__ void publish_flag(unsigned long long *flag, unsigned long long epoch, bool one) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    if (threadIdx.x == 0) {
+    if (one) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __hip_atomic_store((gu64 *)(flag), epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
@@ -363,6 +368,12 @@ __device__ __forceinline__ long long take_ticket(const Tickets &tk, unsigned y, 
     if (t > units + (long long)gridDim.x) ticket_fault(tk, TK_RANGE);
     return -1;
 }
+// a wave-uniform 64-bit value the compiler computed per lane, into SGPRs
+__device__ __forceinline__ long long uniform64(long long v) {
+    const int lo = __builtin_amdgcn_readfirstlane((int)(v & 0xffffffffll));
+    const int hi = __builtin_amdgcn_readfirstlane((int)(v >> 32));
+    return (long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
+}
 // thread 0 of workgroup index pb (0-based among the ticketed workgroups):
 // the unit (b << 2) | m of block b -- m = 0 the whole block; with split > 0
 // the last `split` blocks of every range are dealt as two half units each,
@@ -416,9 +427,7 @@ __device__ __forceinline__ long long wg_take_unit(const Tickets &tk, long long n
     }
     __syncthreads();
     const long long v = *slot;
-    const int lo = __builtin_amdgcn_readfirstlane((int)(v & 0xffffffffll));
-    const int hi = __builtin_amdgcn_readfirstlane((int)(v >> 32));
-    return (long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
+    return uniform64(v);
 }
 // whole blocks only: the block index, -1 when none is left
 __device__ __forceinline__ long long wg_take_block(const Tickets &tk, long long nb, long long k0, long long pb,
@@ -524,8 +533,10 @@ __device__ __forceinline__ void tw_powers(pk::v2f (&v)[N], pk::v2f w, pk::v2f sw
 
 // first half: radix-16 over m, twiddles, transpose write.  PK: packed-f32
 // butterflies and twiddle multiplies (pk.hpp).  TWR: twiddles by recurrence
-// from W1024^t (tw_powers) instead of 15 table reads.
-template <int PK = 0, bool TWR = false>
+// from W1024^t (tw_powers) instead of 15 table reads.  FMA (with PK = 0, no
+// TWR): the 16-point transform with fused-FMA butterflies (fft16_fma,
+// common.hpp) -- the C = 1024 kernels of frame_td.hip, every one of them.
+template <int PK = 0, bool TWR = false, bool FMA = false>
 __device__ __forceinline__ void row_fft_a(float2 (&a)[16], int t, float2 *T, const float2 *tw1) {
     if constexpr (TWR) {
         pk::v2f v[16];
@@ -557,15 +568,20 @@ __device__ __forceinline__ void row_fft_a(float2 (&a)[16], int t, float2 *T, con
         for (int k2 = 0; k2 < 16; ++k2) T[swz(k2, t)] = pk::F(v[k2]);
         return;
     }
-    fft_reg<16, false>(a);
+    static_assert(!FMA || (PK == 0 && !TWR), "fft16_fma is the plain-f32 table-twiddle path's");
+    if constexpr (FMA)
+        fft16_fma(a);
+    else
+        fft_reg<16, false>(a);
 #pragma unroll
     for (int k2 = 1; k2 < 16; ++k2) a[k2] = cmul(a[k2], tw1[(k2 - 1) * 64 + t]);
 #pragma unroll
     for (int k2 = 0; k2 < 16; ++k2) T[swz(k2, t)] = a[k2];
 }
 // second half: transpose read, radix-16, twiddles, quad DFT.  TWR: the
-// twiddles g(a) W64^(a k) by recurrence from tw2[4 + a] = g(a) W64^a.
-template <int PK = 0, bool TWR = false>
+// twiddles g(a) W64^(a k) by recurrence from tw2[4 + a] = g(a) W64^a.  FMA: as
+// in row_fft_a.
+template <int PK = 0, bool TWR = false, bool FMA = false>
 __device__ __forceinline__ void row_fft_b(int t, float2 *T, const float2 *tw2, float2 (&x)[16]) {
     wave_lds_sync();
     const int q = t >> 2, qa = t & 3;
@@ -600,7 +616,11 @@ __device__ __forceinline__ void row_fft_b(int t, float2 *T, const float2 *tw2, f
 #pragma unroll
         for (int m = 0; m < 16; ++m) x[m] = pk::F(v[m]);
     } else {
-        fft_reg<16, false>(x);
+        static_assert(!FMA || (PK == 0 && !TWR), "fft16_fma is the plain-f32 table-twiddle path's");
+        if constexpr (FMA)
+            fft16_fma(x);
+        else
+            fft_reg<16, false>(x);
         x[0] = float2{g * x[0].x, g * x[0].y};
 #pragma unroll
         for (int k = 1; k < 16; ++k) x[k] = cmul(x[k], tw2[k * 4 + qa]);
