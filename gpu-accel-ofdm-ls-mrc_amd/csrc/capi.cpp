@@ -760,6 +760,60 @@ int ofdm_frame_export_estimate(const void *d_ws, size_t ws_bytes_, long long nfr
                      "ofdm_frame_export_estimate");
 }
 
+// Soft output: what both calls check before any device work, then the
+// registry (a full estimate of this geometry, time- or frequency-domain: P is
+// bin-indexed in all of them).  Returns 1 for the nframes == 0 no-op.
+static int soft_args(const char *fn, const void *d_z, long long nframes, int S, int R, int C, const void *d_ws,
+                     size_t ws_bytes_, int modulation, const void *d_nv, const float **P) {
+    if (modulation != OFDM_MOD_QPSK && modulation != OFDM_MOD_QAM16 && modulation != OFDM_MOD_QAM64 &&
+        modulation != OFDM_MOD_QAM256)
+        return fail(OFDM_E_ARG, "%s: modulation=%d (OFDM_MOD_QPSK 2, _QAM16 4, _QAM64 6 or _QAM256 8)", fn, modulation);
+    if (nframes < 0) return fail(OFDM_E_ARG, "%s: nframes < 0", fn);
+    if (S < 2) return fail(OFDM_E_ARG, "%s: S=%d, a frame needs a pilot and >= 1 data symbol", fn, S);
+    if (R < 1) return fail(OFDM_E_ARG, "%s: R=%d < 1", fn, R);
+    if (!valid_c(C)) return fail(OFDM_E_UNSUPPORTED, "%s: C=%d out of [2, 8192]", fn, C);
+    if (nframes == 0) return 1;
+    if (!d_z || !d_nv || !d_ws) return fail(OFDM_E_ARG, "%s: null pointer", fn);
+    if (!aligned(d_z, 16)) return fail(OFDM_E_ARG, "%s: d_z must be 16-byte aligned", fn);
+    if (!aligned(d_nv, 4)) return fail(OFDM_E_ARG, "%s: d_noise_var must be 4-byte aligned", fn);
+    if (!ofdm::soft_demap_supported(nframes, S, C))
+        return fail(OFDM_E_UNSUPPORTED, "%s: nframes=%lld S=%d C=%d: a frame's (S-1)*(C-1) elements and the batch's "
+                                        "tiles of 1024 must stay below 2^31", fn, nframes, S, C);
+    int rc = ws_check(d_ws, ws_bytes_, nframes, S, R, C, true, fn);
+    if (rc) return rc;
+    Workspace w;
+    if ((rc = carve(const_cast<void *>(d_ws), ws_bytes_, nframes, S, R, C, !fused_c(C), w))) return rc;
+    *P = w.P;
+    return OFDM_OK;
+}
+
+int ofdm_frame_noise_estimate(const ofdm_cf32 *d_z, long long nframes, int S, int R, int C, const void *d_ws,
+                              size_t ws_bytes_, int modulation, float *d_noise_var, ofdm_stream_t stream) {
+    static const char *fn = "ofdm_frame_noise_estimate";
+    const float *P = nullptr;
+    if (int rc = soft_args(fn, d_z, nframes, S, R, C, d_ws, ws_bytes_, modulation, d_noise_var, &P))
+        return rc > 0 ? OFDM_OK : rc;
+    return hip_check(ofdm::launch_noise_estimate(F2(d_z), nframes, S, C, P, modulation, d_noise_var, hs(stream)), fn);
+}
+
+int ofdm_frame_soft_demap(const ofdm_cf32 *d_z, long long nframes, int S, int R, int C, const void *d_ws,
+                          size_t ws_bytes_, int modulation, const float *d_noise_var, int llr_format,
+                          float llr_scale, void *d_llr, ofdm_stream_t stream) {
+    static const char *fn = "ofdm_frame_soft_demap";
+    if (llr_format != OFDM_LLR_F32 && llr_format != OFDM_LLR_I8)
+        return fail(OFDM_E_ARG, "%s: llr_format=%d (OFDM_LLR_F32 0 or OFDM_LLR_I8 1)", fn, llr_format);
+    if (llr_format == OFDM_LLR_I8 && !(llr_scale > 0.f && llr_scale <= 3.402823466e38f))
+        return fail(OFDM_E_ARG, "%s: llr_scale=%g, OFDM_LLR_I8 needs a positive finite scale", fn, (double)llr_scale);
+    const float *P = nullptr;
+    if (int rc = soft_args(fn, d_z, nframes, S, R, C, d_ws, ws_bytes_, modulation, d_noise_var, &P))
+        return rc > 0 ? OFDM_OK : rc;
+    if (!d_llr) return fail(OFDM_E_ARG, "%s: null pointer", fn);
+    if (!aligned(d_llr, 16)) return fail(OFDM_E_ARG, "%s: d_llr must be 16-byte aligned", fn);
+    return hip_check(ofdm::launch_soft_demap(F2(d_z), nframes, S, C, P, d_noise_var, modulation, llr_format,
+                                             llr_scale, d_llr, hs(stream)),
+                     fn);
+}
+
 int ofdm_synth_frames(ofdm_cf32 *d_iq, long long nframes, int S, int R, int C, int prefix,
                       const ofdm_cf32 *d_X, unsigned long long seed, long long frame0,
                       float noise_std, int freq_domain, int r0, ofdm_stream_t stream) {

@@ -174,6 +174,19 @@ hipError_t launch_dist_sqrd(const float2 *H, int R, int K, float *P, hipStream_t
 hipError_t launch_export_estimate(const float2 *Hc, const float *P, int R, int C, bool lane_order,
                                   float2 *Hconj, float *Hsqrd, hipStream_t s);
 
+// Soft output (soft_demap.hip).  z: the demodulated [nframes][S-1][K] array
+// (16-B aligned), P: the workspace's bin-indexed |H|^2 [nframes][C], bps in
+// {2, 4, 6, 8}.  noise_estimate: nv[f] = mean of P |Z - slice(Z)|^2 over frame
+// f.  soft_demap: llr [nframes][S-1][K][bps] (16-B aligned), fmt 0 = float,
+// 1 = signed byte clamp(rint(llr * llr_scale), -127, 127).  Both need
+// soft_demap_supported (a frame's (S-1)*K and the grid below 2^31), else
+// hipErrorInvalidValue.
+bool soft_demap_supported(long long nframes, int S, int C);
+hipError_t launch_noise_estimate(const float2 *z, long long nframes, int S, int C, const float *P, int bps,
+                                 float *nv, hipStream_t s);
+hipError_t launch_soft_demap(const float2 *z, long long nframes, int S, int C, const float *P, const float *nv,
+                             int bps, int fmt, float llr_scale, void *out, hipStream_t s);
+
 // Synthetic frames: time-domain (freq_domain=0, rows of C+prefix with a
 // cyclic prefix) or frequency-domain (freq_domain=1, rows of C) IQ.
 hipError_t launch_synth(float2 *iq, long long nframes, int S, int R, int C, int prefix,

@@ -58,6 +58,8 @@ _SIGS = {
     "ofdm_frame_mrc_partial": (_I, [_P, _LL, _I, _I, _I, _I, _P, _c.c_size_t, _P, _P]),
     "ofdm_frame_mrc_partial_range": (_I, [_P, _LL, _LL, _LL, _I, _I, _I, _I, _P, _c.c_size_t, _P, _P]),
     "ofdm_frame_export_estimate": (_I, [_P, _c.c_size_t, _LL, _I, _I, _I, _LL, _P, _P, _P]),
+    "ofdm_frame_noise_estimate": (_I, [_P, _LL, _I, _I, _I, _P, _c.c_size_t, _I, _P, _P]),
+    "ofdm_frame_soft_demap": (_I, [_P, _LL, _I, _I, _I, _P, _c.c_size_t, _I, _P, _I, _c.c_float, _P, _P]),
     "ofdm_symbols_demod": (_I, [_P, _LL, _I, _I, _I, _P, _c.c_size_t, _LL, _P, _P]),
     "ofdm_synth_frames": (_I, [_P, _LL, _I, _I, _I, _I, _P, _c.c_ulonglong, _LL, _c.c_float,
                                _I, _I, _P]),
@@ -463,6 +465,38 @@ def frame_export_estimate(ws, F, S, R, C, frame=0, stream=None):
     _check(lib().ofdm_frame_export_estimate(_dptr(ws), ws.numel(), F, S, R, C, frame, _dptr(H), _dptr(P),
                                             _stream(stream)), "ofdm_frame_export_estimate")
     return H, P
+
+
+MOD_QPSK, MOD_QAM16, MOD_QAM64, MOD_QAM256 = 2, 4, 6, 8  # OFDM_MOD_*: bits per symbol
+_LLR_FORMATS = {"f32": 0, "i8": 1}  # OFDM_LLR_*
+
+
+def frame_noise_estimate(z, ws, F, S, R, C, modulation, out=None, stream=None):
+    """Decision-directed noise variance of every frame, (F,) float32: the mean
+    of P |Z - slice(Z)|^2 over the frame's demodulated symbols z (F, S-1, K),
+    P from the estimate in ws (any full estimate of this F, S, R, C)."""
+    import torch
+    if out is None:
+        out = torch.empty(F, dtype=torch.float32, device=z.device)
+    _check(lib().ofdm_frame_noise_estimate(_dptr(z, "z"), F, S, R, C, _dptr(ws, "ws"), ws.numel(), modulation,
+                                           _dptr(out, "out"), _stream(stream)), "ofdm_frame_noise_estimate")
+    return out
+
+
+def frame_soft_demap(z, ws, F, S, R, C, modulation, noise_var, fmt="f32", scale=1.0, out=None, stream=None):
+    """Max-log LLRs of the demodulated symbols z (F, S-1, K) -> (F, S-1, K, bps),
+    float32 (fmt "f32") or int8 clamp(rint(llr * scale), -127, 127) (fmt "i8");
+    llr > 0 <=> bit 0.  noise_var: (F,) float32 on the device."""
+    import torch
+    if fmt not in _LLR_FORMATS:
+        raise OfdmError(f"fmt must be 'f32' or 'i8', not {fmt!r}")
+    if out is None:
+        out = torch.empty((F, S - 1, C - 1, modulation), dtype=torch.float32 if fmt == "f32" else torch.int8,
+                          device=z.device)
+    _check(lib().ofdm_frame_soft_demap(_dptr(z, "z"), F, S, R, C, _dptr(ws, "ws"), ws.numel(), modulation,
+                                       _dptr(noise_var, "noise_var"), _LLR_FORMATS[fmt], scale, _dptr(out, "out"),
+                                       _stream(stream)), "ofdm_frame_soft_demap")
+    return out
 
 
 def synth_frames(F, S, R, C, X, prefix=0, seed=1234, frame0=0, noise_std=0.01,

@@ -142,7 +142,8 @@ int ofdm_dist_sqrd(const ofdm_cf32 *d_H, int R, int K, float *d_Hsqrd, ofdm_stre
  * {1024, 2048, 4096}
  * (no fused kernel), a frequency-domain staging buffer of at most 256 MiB.
  * A workspace carries the estimate of ONE geometry: the calls that consume it
- * (ofdm_frame_combine, ofdm_frame_mrc_partial, ofdm_frame_export_estimate)
+ * (ofdm_frame_combine, ofdm_frame_mrc_partial, ofdm_frame_export_estimate,
+ * ofdm_frame_noise_estimate, ofdm_frame_soft_demap)
  * must pass the nframes, S, R, C and ws_bytes of the call that filled it, and
  * return OFDM_E_ARG otherwise (checked per process, on the host, by a registry
  * keyed on d_ws).  An estimate call clears the workspace's entry before it
@@ -238,6 +239,56 @@ int ofdm_frame_combine(const ofdm_cf32 *d_iq, long long nframes, int S, int R, i
  * lane order. */
 int ofdm_frame_export_estimate(const void *d_ws, size_t ws_bytes, long long nframes, int S, int R, int C,
                                long long frame, ofdm_cf32 *d_Hconj, float *d_Hsqrd, ofdm_stream_t stream);
+
+/* Soft-decision output (no reference counterpart; added without a version
+ * step: OFDM_LSMRC_VERSION stays 2).  Both calls read d_z, the demodulated
+ * [nframes][S-1][K] array of a frame call (rotated order, 16-B aligned), and
+ * the |H|^2 sums its estimate left in d_ws: P[j] = sum_r |H[r][j]|^2, stored
+ * by FFT bin for every C and every estimator, so a workspace filled by any
+ * FULL estimate of the same nframes, S, R, C, ws_bytes is accepted
+ * (ofdm_frame_demod, _estimate, _demod_freq, _estimate_freq, _demod_freq_mfma).
+ * OFDM_E_ARG for an antenna-split partial estimate (ofdm_frame_ls_partial),
+ * another geometry, a workspace without an estimate, a modulation or format
+ * not listed here, a null pointer with nframes > 0, or OFDM_LLR_I8 with an
+ * llr_scale that is not positive and finite; nframes == 0 is a no-op
+ * (OFDM_OK).  The workspace is only read: no work tickets, and the sticky
+ * device status is neither consulted nor cleared.
+ *
+ * Constellations: Gray-mapped, unit average energy, 3GPP TS 38.211 5.1.3-5.1.6;
+ * `modulation` is the number of bits per symbol.  For the element at
+ * (f, s, k), whose subcarrier is j (the inverse of the output rotation
+ * above), d_llr[((f*(S-1) + s)*K + k)*bps + b], b = 0..bps-1:
+ *     llr[2i]   = P[f][j] / noise_var[f] * lambda_i(Re Z)
+ *     llr[2i+1] = P[f][j] / noise_var[f] * lambda_i(Im Z)
+ * with, a = 1/sqrt(2), 1/sqrt(10), 1/sqrt(42), 1/sqrt(170) for bps = 2, 4,
+ * 6, 8 and m_i = 2^(bps/2 - 1 - i),
+ *     t_0 = x,  t_i = 2 a m_i - |t_(i-1)|,  lambda_i(x) = 4 a t_i
+ *     (16-QAM: 4a x, 4a (2a - |x|); 64-QAM: 4a x, 4a (4a - |x|),
+ *      4a (2a - ||x| - 4a|); 256-QAM: 8a, 4a, 2a nested likewise).
+ * llr > 0 <=> bit 0 more likely.  This is the MAX-LOG approximation in its
+ * recursive constant-slope form, not the exact log-sum.  ofdm_synth_frames'
+ * QPSK puts the positive axis where its data bit is SET, the complement of
+ * the 38.211 bit: there a hard decision llr < 0 means generator bit 0.
+ * An element whose P or noise_var is not positive and finite gets llr = 0.
+ *   OFDM_LLR_F32: d_llr holds floats.
+ *   OFDM_LLR_I8:  d_llr holds signed bytes clamp(rint(llr * llr_scale), -127,
+ *                 127), round-to-nearest-even; -128 is never produced.
+ * d_llr: nframes*(S-1)*K*bps values, 16-B aligned.
+ *
+ * ofdm_frame_noise_estimate: decision-directed, per frame,
+ *     d_noise_var[f] = mean over (s, k) of P[f][j] |Z - slice(Z)|^2,
+ * slice = the nearest point of the constellation; elements whose P is 0 or
+ * not finite are skipped.  Z - X has variance sigma^2 / P[j], so this
+ * estimates the per-antenna bin noise INCLUDING the LS estimate's own error
+ * (about twice sigma^2 with equal-energy pilots and data) -- the quantity the
+ * LLR scale needs.  Fixed-order reduction: bit-identical from run to run. */
+enum { OFDM_MOD_QPSK = 2, OFDM_MOD_QAM16 = 4, OFDM_MOD_QAM64 = 6, OFDM_MOD_QAM256 = 8 }; /* = bits/symbol */
+enum { OFDM_LLR_F32 = 0, OFDM_LLR_I8 = 1 };
+int ofdm_frame_noise_estimate(const ofdm_cf32 *d_z, long long nframes, int S, int R, int C, const void *d_ws,
+                              size_t ws_bytes, int modulation, float *d_noise_var, ofdm_stream_t stream);
+int ofdm_frame_soft_demap(const ofdm_cf32 *d_z, long long nframes, int S, int R, int C, const void *d_ws,
+                          size_t ws_bytes, int modulation, const float *d_noise_var /* [nframes], device */,
+                          int llr_format, float llr_scale, void *d_llr, ofdm_stream_t stream);
 
 /* Per-symbol receiver (gpuLS::demodOneSymbol, gpuLS.cu:410-473, which runs
  * cuFFT + multiplyWithChannelConj + combineForMRC + a CPU shift per symbol):
