@@ -50,10 +50,9 @@ size_t up256(size_t x) { return (x + 255) & ~size_t(255); }
 // fused one-pass kernels exist for these FFT sizes
 bool fused_c(int C) { return C == 1024 || C == 2048 || C == 4096; }
 // sizes whose workspace estimate is in a receiver's lane order: the fused
-// ones and C = 128 / 256 / 512 / 1536 / 3072 / 6144 (staged pilot FFT, then
-// k_ls_* / k_mrc_td* of frame_td_fft512.hip)
-bool small_c(int C) { return C == 128 || C == 256 || C == 512; }
-bool lane_c(int C) { return fused_c(C) || small_c(C) || C == 1536 || C == 3072 || C == 6144; }
+// ones and the FFT512 family (staged pilot FFT, then k_ls_* / k_mrc_td* of
+// frame_td_fft512.hip)
+bool lane_c(int C) { return fused_c(C) || ofdm::lane512_supported(C); }
 
 // fused time-domain kernels by C (fused_c(C) must hold)
 hipError_t ls_fused(const float2 *iq, long long F, int S, int R, int C, int prefix, const float2 *X,
@@ -291,6 +290,7 @@ int check_frame_args(const void *in, long long F, int S, int R, int C, int prefi
 int td_staged(const float2 *iq, long long F, int S, int R, int C, int prefix, const float2 *X,
               const Workspace &w, float2 *out, int mode, hipStream_t s) {
     const long long frame_in = (long long)S * R * (C + prefix);
+    const bool lane512 = ofdm::lane512_supported(C);
     hipError_t e;
     if (mode == 0 || mode == 2) {
         // the staging buffer holds w.chunk whole frames = w.chunk * S frames' pilot rows
@@ -300,28 +300,18 @@ int td_staged(const float2 *iq, long long F, int S, int R, int C, int prefix, co
             e = ofdm::launch_fft_any_b(iq + f0 * frame_in, C + prefix, R, frame_in, prefix, w.staging, C, 0, n * R,
                                        C, false, 1.f, s);
             if (e != hipSuccess) return hip_check(e, "fft (pilot rows)");
-            e = C == 1536   ? ofdm::launch_ls_1536(w.staging, n, R, X, w.Hc + f0 * pilot, w.P + f0 * C, s)
-                : C == 3072 ? ofdm::launch_ls_3072(w.staging, n, R, X, w.Hc + f0 * pilot, w.P + f0 * C, s)
-                : C == 6144 ? ofdm::launch_ls_6144(w.staging, n, R, X, w.Hc + f0 * pilot, w.P + f0 * C, s)
-                : small_c(C) ? ofdm::launch_ls_small(C, w.staging, n, R, X, w.Hc + f0 * pilot, w.P + f0 * C, s)
-                            : ofdm::launch_ls_freq(w.staging, pilot, n, R, C, X, w.Hc + f0 * pilot, pilot, C, 1,
-                                                   w.P + f0 * C, C, 1, s);
+            e = lane512 ? ofdm::launch_ls_lane512(C, w.staging, n, R, X, w.Hc + f0 * pilot, w.P + f0 * C, s)
+                        : ofdm::launch_ls_freq(w.staging, pilot, n, R, C, X, w.Hc + f0 * pilot, pilot, C, 1,
+                                               w.P + f0 * C, C, 1, s);
             if (e != hipSuccess) return hip_check(e, "ls_freq");
         }
     }
     if (mode == 2) return OFDM_OK;
-    if (C == 1536)
-        return hip_check(ofdm::launch_mrc_td1536(iq, F, S, R, prefix, w.Hc, w.P, out, mode == 1 ? 1 : 0, s),
-                         "mrc_td1536");
-    if (C == 3072)
-        return hip_check(ofdm::launch_mrc_td3072(iq, F, S, R, prefix, w.Hc, w.P, out, mode == 1 ? 1 : 0, s),
-                         "mrc_td3072");
-    if (C == 6144)
-        return hip_check(ofdm::launch_mrc_td6144(iq, F, S, R, prefix, w.Hc, w.P, out, mode == 1 ? 1 : 0, s),
-                         "mrc_td6144");
-    if (small_c(C))
-        return hip_check(ofdm::launch_mrc_small(C, iq, F, S, R, prefix, w.Hc, w.P, out, mode == 1 ? 1 : 0, s),
-                         "mrc_small");
+    if (lane512) {
+        char what[16];  // the kernel's name in the error text: mrc_td1536 / 3072 / 6144, mrc_small below
+        snprintf(what, sizeof what, C < 1024 ? "mrc_small" : "mrc_td%d", C);
+        return hip_check(ofdm::launch_mrc_lane512(C, iq, F, S, R, prefix, w.Hc, w.P, out, mode == 1 ? 1 : 0, s), what);
+    }
     return hip_check(ofdm::launch_mrc_any(iq, F, S, R, C, prefix, w.Hc, w.P, out, mode == 1 ? 1 : 0, s),
                      "mrc_any");
 }

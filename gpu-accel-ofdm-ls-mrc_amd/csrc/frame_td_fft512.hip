@@ -1,9 +1,13 @@
 // frame_td_fft512.hip -- fused receivers for the FFT sizes built on one
 // in-register FFT512 per wave: C = 1536 (LTE's 15 MHz size), 3072 (a wave
-// pair), 6144 (a wave quad) and 512 itself.  One HBM pass over the IQ, as the
-// power-of-two receivers (demodOneFrameCUDA, gpuLS.cu:575-675, without its
-// cuFFT round trips), replacing the generic any-C kernel (fft_any.hip) at
-// these sizes.
+// pair), 6144 (a wave quad), 512 itself and 256 / 128.  One HBM pass over the
+// IQ, as the power-of-two receivers (demodOneFrameCUDA, gpuLS.cu:575-675,
+// without its cuFFT round trips), replacing the generic any-C kernel
+// (fft_any.hip) at these sizes.  The pieces every size shares (the FFT512,
+// its row twiddles, the radix-3 step, the output epilogue, the LS body) are
+// in namespace lane512; which bin a lane's slot holds is lane_layout.hpp's;
+// the host side is one table (kLane512) behind launch_ls_lane512 /
+// launch_mrc_lane512.
 //
 // C = 1536: one 64-lane wave transforms one antenna row held in registers,
 // 24 samples per lane (lane t: x[t + 64 m'], m' < 24):
@@ -17,26 +21,25 @@
 //   * packed f32 complex arithmetic (pk.hpp); the per-lane twiddles of passes
 //     A and B1 are row invariants held in registers, the DIF twiddles come
 //     from a W1536 table in LDS.
-// Lane L therefore owns the 24 bins 3 (s + 8 c + 64 d) + j, slot i = 8 j + d.
-// The channel estimate is kept in that "lane order" (k_ls_1536 writes it:
-// per (frame, antenna) slot i of lane L at i * 64 + L, one coalesced 512-B
-// wave load per slot); P stays bin-indexed [F][C].  A wave owns one data
-// symbol at a time and walks its R rows in order (matrixMultThenSum order,
-// cpuLS.hpp:187-208), the next row's 24 samples in flight during the current
-// row's transform; no workgroup barrier after the table fill.
+// Lane L therefore owns the 24 bins 3 (s + 8 c + 64 d) + j, slot i = 8 j + d
+// (lane::bin512).  The channel estimate is kept in that "lane order"
+// (k_ls_1536 writes it: per (frame, antenna) slot i of lane L at i * 64 + L,
+// one coalesced 512-B wave load per slot); P stays bin-indexed [F][C].  A
+// wave owns one data symbol at a time and walks its R rows in order
+// (matrixMultThenSum order, cpuLS.hpp:187-208), the next row's 24 samples in
+// flight during the current row's transform; no workgroup barrier after the
+// table fill.
 #include "common.hpp"
+#include "lane_layout.hpp"
 #include "launch.hpp"
 #include "pk.hpp"
 
 namespace ofdm {
-namespace td1536 {
+namespace lane512 {
 
 using pk::v2f;
-constexpr int C = 1536, K = C - 1;
 constexpr int PA = 72;               // transpose image: 8 rows of 64 + 8 (conflict-free reads)
 constexpr int TS = 8 * PA;           // per-wave image, 4.5 KiB
-constexpr int WAVES = 4;
-constexpr int NT = 64 * WAVES;
 
 __device__ __forceinline__ void wsync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -48,11 +51,6 @@ __device__ __forceinline__ void wsync() {
 // per-frame channel estimates every data symbol of the frame re-reads.
 __device__ __forceinline__ float2 ld_stream(const float2 *p) {
     return __builtin_bit_cast(float2, __builtin_nontemporal_load(reinterpret_cast<const unsigned long long *>(p)));
-}
-
-// bin of lane L's slot i (i = 8 j + d)
-__device__ __forceinline__ int bin_of(int L, int i) {
-    return 3 * ((L >> 3) + 8 * (L & 7) + 64 * (i & 7)) + (i >> 3);
 }
 
 // The two FFT64 passes of fft512: lane t holds v[s] = A_s[t] (8 sequences of
@@ -86,6 +84,109 @@ __device__ __forceinline__ void fft512(v2f (&v)[8], float2 *T, int L, const v2f 
     fft64x8(v, T, L, twB);
 }
 
+// The row invariants of lane L: twA[k - 1] = W_N^{L k}, k < NP (pass A: a
+// DFT_NP per lane of an N = 64 NP point transform), twB[k - 1] = W64^{a k},
+// a = L & 7 (pass B1).
+template <int NP>
+__device__ __forceinline__ void row_twiddles(int L, v2f (&twA)[NP > 1 ? NP - 1 : 1], v2f (&twB)[7]) {
+    constexpr int N = 64 * NP;
+#pragma unroll
+    for (int k = 1; k < NP; ++k) {
+        double sn, cs;
+        sincospi(-2.0 * (double)((L * k) % N) / (double)N, &sn, &cs);
+        twA[k - 1] = v2f{(float)cs, (float)sn};
+    }
+#pragma unroll
+    for (int k = 1; k < 8; ++k) {
+        double sn, cs;
+        sincospi(-2.0 * (double)(((L & 7) * k) % 64) / 64.0, &sn, &cs);
+        twB[k - 1] = v2f{(float)cs, (float)sn};
+    }
+}
+
+// Radix-3 DIF in registers: x[8 i + m] = x[n + (C / 3) i], n = n0 + 64 m ->
+// u[j][m] = W_C^{n j} sum_i x[n + (C / 3) i] W3^{i j}; tab[e] = W_C^e, e <= 2 n.
+__device__ __forceinline__ void radix3_dif(const float2 (&x)[24], v2f (&u)[3][8], const float2 *tab, int n0) {
+    const float r3 = 0.86602540378443865f;  // sin(2 pi / 3)
+#pragma unroll
+    for (int m = 0; m < 8; ++m) {
+        const v2f a0 = pk::V(x[m]), a1 = pk::V(x[m + 8]), a2 = pk::V(x[m + 16]);
+        const v2f sm = a1 + a2, df = a1 - a2;
+        const v2f t0 = a0 - sm * (v2f){0.5f, 0.5f};
+        const v2f jd = v2f{df.y * r3, -df.x * r3};  // -i sin(2 pi/3) (a1 - a2)
+        const int n = n0 + 64 * m;
+        u[0][m] = a0 + sm;
+        u[1][m] = pk::cmul(t0 + jd, pk::V(tab[n]));
+        u[2][m] = pk::cmul(t0 - jd, pk::V(tab[2 * n]));
+    }
+}
+
+// One data symbol's output from a lane's NS accumulators, bin_of(i) the bin
+// of slot i: mode 0 acc / P through out_pos, mode 1 the raw numerator.  The
+// wave-pair and wave-quad kernels form bin_of from lane_here(): output
+// offsets hoisted out of the symbol loop were spilled and reloaded behind a
+// vmcnt(0) that drained the next symbol's row load.
+template <int C, int NS, typename BinOf>
+__device__ __forceinline__ void store_symbol(const v2f (&acc)[NS], BinOf bin_of, const float *Pf, float2 *o, int mode) {
+    constexpr int K = C - 1;
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+        const int b = bin_of(i);
+        if (b == 0) continue;  // the DC bin carries no subcarrier
+        const float2 a = pk::F(acc[i]);
+        if (mode == 0) {
+            const float p = Pf[b];
+            o[out_pos(b - 1, K)] = float2{a.x * __builtin_amdgcn_rcpf(p), a.y * __builtin_amdgcn_rcpf(p)};
+        } else {
+            o[b - 1] = a;
+        }
+    }
+}
+
+// LS from the FFT'd pilot rows (staging, bin order, frame stride R C):
+// Hc = conj(Y / X) in the lane order of C's MRC kernel (lane::hc_pos),
+// P = sum_r |Hc|^2 (rows in order, bin layout with P[0] = 1 and a zero DC
+// estimate), findHs + findDistSqrd (gpuLS.cu:158-209, cpuLS.hpp:211-244) as
+// k_ls_freq.
+template <int C>
+__device__ __forceinline__ void ls_lane(const float2 *__restrict__ Y, int R, const float2 *__restrict__ X,
+                                        float2 *__restrict__ Hl, float *__restrict__ P) {
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= C) return;
+    const long long f = blockIdx.y;
+    const float2 *Yf = Y + f * (long long)R * C;
+    float2 *Hf = Hl + f * (long long)R * C + lane::hc_pos(C, b);
+    float p = 0.f;
+    if (b == 0) {
+        for (int r = 0; r < R; ++r) Hf[(long long)r * C] = float2{0.f, 0.f};
+        p = 1.f;
+    } else {
+        const float2 x = X[b - 1];
+        for (int r = 0; r < R; ++r) {
+            const float2 h = ls_conj(Yf[(long long)r * C + b], x);
+            Hf[(long long)r * C] = h;
+            p = (r == 0) ? (h.x * h.x) + (h.y * h.y) : p + (h.x * h.x) + (h.y * h.y);
+        }
+    }
+    P[f * C + b] = p;
+}
+
+#define OFDM_K_LS(CC)                                                                                       \
+    __global__ void __launch_bounds__(256) k_ls_##CC(const float2 *__restrict__ Y, int R,                   \
+                                                     const float2 *__restrict__ X, float2 *__restrict__ Hl, \
+                                                     float *__restrict__ P) {                               \
+        lane512::ls_lane<CC>(Y, R, X, Hl, P);                                                               \
+    }
+
+}  // namespace lane512
+
+namespace td1536 {
+
+using namespace lane512;
+constexpr int C = 1536, K = C - 1;
+constexpr int WAVES = 4;
+constexpr int NT = 64 * WAVES;
+
 __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2)))
 k_mrc_td1536(const float2 *__restrict__ iq, long long nframes, int S, int R, int prefix, const float2 *__restrict__ Hl,
              const float *__restrict__ P, float2 *__restrict__ out, int mode) {
@@ -99,7 +200,8 @@ k_mrc_td1536(const float2 *__restrict__ iq, long long nframes, int S, int R, int
     __syncthreads();
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), L = threadIdx.x & 63;  // w uniform: q, f, row pointers scalar
     float2 *T = img[w];
-    // row invariants: W512^{t s} = W1536^{3 t s} (t = L), W64^{a c} = W1536^{24 a c} (a = L & 7)
+    // row invariants from the table (not row_twiddles' sincospi):
+    // W512^{t s} = W1536^{3 t s} (t = L), W64^{a c} = W1536^{24 a c} (a = L & 7)
     v2f twA[7], twB[7];
 #pragma unroll
     for (int k = 1; k < 8; ++k) {
@@ -108,7 +210,6 @@ k_mrc_td1536(const float2 *__restrict__ iq, long long nframes, int S, int R, int
     }
     const int nsd = S - 1;
     const long long Cp = C + prefix, nq = nframes * nsd, nw = (long long)gridDim.x * WAVES;
-    const float r3 = 0.86602540378443865f;  // sin(2 pi / 3)
     auto row_ptr = [&](long long q, int r) {
         const long long f = q / nsd, s = 1 + q % nsd;
         return iq + ((f * S + s) * R + r) * Cp + prefix;
@@ -128,19 +229,8 @@ k_mrc_td1536(const float2 *__restrict__ iq, long long nframes, int S, int R, int
 #pragma unroll
         for (int i = 0; i < 24; ++i) acc[i] = v2f{0.f, 0.f};
         for (int r = 0; r < R; ++r) {
-            // radix-3 DIF in registers
             v2f u[3][8];
-#pragma unroll
-            for (int m = 0; m < 8; ++m) {
-                const v2f a0 = pk::V(x[m]), a1 = pk::V(x[m + 8]), a2 = pk::V(x[m + 16]);
-                const v2f sm = a1 + a2, df = a1 - a2;
-                const v2f t0 = a0 - sm * (v2f){0.5f, 0.5f};
-                const v2f jd = v2f{df.y * r3, -df.x * r3};  // -i sin(2 pi/3) (a1 - a2)
-                const int n = L + 64 * m;
-                u[0][m] = a0 + sm;
-                u[1][m] = pk::cmul(t0 + jd, pk::V(tab[n]));
-                u[2][m] = pk::cmul(t0 - jd, pk::V(tab[2 * n]));
-            }
+            radix3_dif(x, u, tab, L);
             // the next row (or the next symbol's first) in flight during the transforms
             {
                 const float2 *b = r + 1 < R ? cur + (r + 1) * Cp : nxt;
@@ -160,49 +250,11 @@ k_mrc_td1536(const float2 *__restrict__ iq, long long nframes, int S, int R, int
                 for (int d = 0; d < 8; ++d) pk::mac(acc[8 * j + d], u[j][d], h[d]);
             }
         }
-        float2 *o = out + q * K;
-        const float *Pf = P + f * C;
-#pragma unroll
-        for (int i = 0; i < 24; ++i) {
-            const int b = bin_of(L, i);
-            if (b == 0) continue;  // the DC bin carries no subcarrier
-            const float2 a = pk::F(acc[i]);
-            if (mode == 0) {
-                const float p = Pf[b];
-                o[out_pos(b - 1, K)] = float2{a.x * __builtin_amdgcn_rcpf(p), a.y * __builtin_amdgcn_rcpf(p)};
-            } else {
-                o[b - 1] = a;
-            }
-        }
+        store_symbol<C>(acc, [&](int i) { return lane::bin512(1, 0, L, i); }, P + f * C, out + q * K, mode);
     }
 }
 
-// LS from the FFT'd pilot rows (staging, bin order, frame stride R C):
-// Hc = conj(Y / X) in lane order, P = sum_r |Hc|^2 (rows in order, bin layout
-// with P[0] = 1 and a zero DC estimate), findHs + findDistSqrd
-// (gpuLS.cu:158-209, cpuLS.hpp:211-244) as k_ls_freq.
-__global__ void __launch_bounds__(256) k_ls_1536(const float2 *__restrict__ Y, int R, const float2 *__restrict__ X,
-                                                 float2 *__restrict__ Hl, float *__restrict__ P) {
-    const int b = blockIdx.x * 256 + threadIdx.x;
-    if (b >= C) return;
-    const long long f = blockIdx.y;
-    const int k = b / 3, j = b - 3 * k, L = 8 * (k & 7) + ((k >> 3) & 7), i = 8 * j + (k >> 6);
-    const float2 *Yf = Y + f * (long long)R * C;
-    float2 *Hf = Hl + f * (long long)R * C + i * 64 + L;
-    float p = 0.f;
-    if (b == 0) {
-        for (int r = 0; r < R; ++r) Hf[(long long)r * C] = float2{0.f, 0.f};
-        p = 1.f;
-    } else {
-        const float2 x = X[b - 1];
-        for (int r = 0; r < R; ++r) {
-            const float2 h = ls_conj(Yf[(long long)r * C + b], x);
-            Hf[(long long)r * C] = h;
-            p = (r == 0) ? (h.x * h.x) + (h.y * h.y) : p + (h.x * h.x) + (h.y * h.y);
-        }
-    }
-    P[f * C + b] = p;
-}
+OFDM_K_LS(1536)
 
 }  // namespace td1536
 
@@ -213,24 +265,20 @@ __global__ void __launch_bounds__(256) k_ls_1536(const float2 *__restrict__ Y, i
 // n + 2048: 24 samples per lane), then one radix-2 DIF step of the three
 // FFT1024s across the pair through LDS (v0 = u[n'] + u[n' + 512] on wave 0,
 // v1 = (u[n'] - u[n' + 512]) W1024^{n'} on wave 1), then three FFT512s per
-// wave (td1536::fft512).  Wave e, lane 8 s + c owns bins 3 (2 k' + e) + j,
-// k' = s + 8 c + 64 d, slot i = 8 j + d; the estimate in that lane order is
-// [e][slot][lane] per antenna row (k_ls_3072).  Two LDS barriers per row (the
-// exchange written / read); the exchange image of a wave doubles as its
-// transpose image once both have read it.
+// wave.  Wave e, lane 8 s + c owns bins 3 (2 k' + e) + j, k' = s + 8 c + 64 d,
+// slot i = 8 j + d; the estimate in that lane order is [e][slot][lane] per
+// antenna row (k_ls_3072).  Two LDS barriers per row (the exchange written /
+// read); the exchange image of a wave doubles as its transpose image once
+// both have read it.
 namespace td3072 {
 
-using pk::v2f;
+using namespace lane512;
 constexpr int C = 3072, K = C - 1;
 constexpr int XS = 24 * 64;  // exchange image per wave (float2): [j][m][t]
 constexpr int NT = 128;      // one pair per workgroup
-static_assert(td1536::TS <= XS, "transpose image fits in the exchange image");
+static_assert(TS <= XS, "transpose image fits in the exchange image");
 
 __device__ __forceinline__ void pair_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-__device__ __forceinline__ int bin_of(int e, int L, int i) {
-    return 3 * (2 * ((L >> 3) + 8 * (L & 7) + 64 * (i & 7)) + e) + (i >> 3);
-}
 
 __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2)))
 k_mrc_td3072(const float2 *__restrict__ iq, long long nframes, int S, int R, int prefix, const float2 *__restrict__ Hl,
@@ -244,19 +292,11 @@ k_mrc_td3072(const float2 *__restrict__ iq, long long nframes, int S, int R, int
     }
     const int e = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), L = threadIdx.x & 63;
     v2f twA[7], twB[7];  // W512^{t s}, W64^{a c}: the FFT512 row invariants
-#pragma unroll
-    for (int k = 1; k < 8; ++k) {
-        double sn, cs;
-        sincospi(-2.0 * (double)((L * k) % 512) / 512.0, &sn, &cs);
-        twA[k - 1] = v2f{(float)cs, (float)sn};
-        sincospi(-2.0 * (double)(((L & 7) * k) % 64) / 64.0, &sn, &cs);
-        twB[k - 1] = v2f{(float)cs, (float)sn};
-    }
+    row_twiddles<8>(L, twA, twB);
     __syncthreads();
     float2 *own = xch[e], *oth = xch[e ^ 1];
     const int nsd = S - 1;
     const long long Cp = C + prefix, nq = nframes * nsd, np = gridDim.x;
-    const float r3 = 0.86602540378443865f;
     auto row_ptr = [&](long long q, int r) {
         const long long f = q / nsd, s = 1 + q % nsd;
         return iq + ((f * S + s) * R + r) * Cp + prefix;
@@ -266,7 +306,7 @@ k_mrc_td3072(const float2 *__restrict__ iq, long long nframes, int S, int R, int
 #pragma unroll
         for (int i = 0; i < 3; ++i)
 #pragma unroll
-            for (int m = 0; m < 8; ++m) x[8 * i + m] = td1536::ld_stream(b + L + 64 * (m + 8 * e + 16 * i));
+            for (int m = 0; m < 8; ++m) x[8 * i + m] = ld_stream(b + L + 64 * (m + 8 * e + 16 * i));
     };
     float2 x[24];
     long long q = blockIdx.x;
@@ -279,17 +319,7 @@ k_mrc_td3072(const float2 *__restrict__ iq, long long nframes, int S, int R, int
         for (int i = 0; i < 24; ++i) acc[i] = v2f{0.f, 0.f};
         for (int r = 0; r < R; ++r) {
             v2f u[3][8];
-#pragma unroll
-            for (int m = 0; m < 8; ++m) {
-                const v2f a0 = pk::V(x[m]), a1 = pk::V(x[m + 8]), a2 = pk::V(x[m + 16]);
-                const v2f sm = a1 + a2, df = a1 - a2;
-                const v2f t0 = a0 - sm * (v2f){0.5f, 0.5f};
-                const v2f jd = v2f{df.y * r3, -df.x * r3};
-                const int n = L + 64 * (m + 8 * e);
-                u[0][m] = a0 + sm;
-                u[1][m] = pk::cmul(t0 + jd, pk::V(tab[n]));
-                u[2][m] = pk::cmul(t0 - jd, pk::V(tab[2 * n]));
-            }
+            radix3_dif(x, u, tab, L + 512 * e);
             {
                 const float2 *b = r + 1 < R ? cur + (r + 1) * Cp : nxt;
                 if (b) load(x, b);
@@ -314,56 +344,17 @@ k_mrc_td3072(const float2 *__restrict__ iq, long long nframes, int S, int R, int
                 v2f h[8];
 #pragma unroll
                 for (int d = 0; d < 8; ++d) h[d] = pk::V(hrow[(8 * j + d) * 64 + L]);
-                td1536::fft512(u[j], own, L, twA, twB);
+                fft512(u[j], own, L, twA, twB);
 #pragma unroll
                 for (int d = 0; d < 8; ++d) pk::mac(acc[8 * j + d], u[j][d], h[d]);
             }
         }
-        float2 *o = out + q * K;
-        const float *Pf = P + f * C;
-        // the lane recomputed here: output offsets hoisted out of the symbol
-        // loop were spilled and reloaded behind a vmcnt(0) that drained the
-        // next symbol's row load
-        const int Le = lane_here();
-#pragma unroll
-        for (int i = 0; i < 24; ++i) {
-            const int b = bin_of(e, Le, i);
-            if (b == 0) continue;
-            const float2 a = pk::F(acc[i]);
-            if (mode == 0) {
-                const float p = Pf[b];
-                o[out_pos(b - 1, K)] = float2{a.x * __builtin_amdgcn_rcpf(p), a.y * __builtin_amdgcn_rcpf(p)};
-            } else {
-                o[b - 1] = a;
-            }
-        }
+        const int Le = lane_here();  // not L: see store_symbol
+        store_symbol<C>(acc, [&](int i) { return lane::bin512(2, e, Le, i); }, P + f * C, out + q * K, mode);
     }
 }
 
-// LS into the lane order of k_mrc_td3072 ([e][slot][lane] per antenna row)
-__global__ void __launch_bounds__(256) k_ls_3072(const float2 *__restrict__ Y, int R, const float2 *__restrict__ X,
-                                                 float2 *__restrict__ Hl, float *__restrict__ P) {
-    const int b = blockIdx.x * 256 + threadIdx.x;
-    if (b >= C) return;
-    const long long f = blockIdx.y;
-    const int k = b / 3, j = b - 3 * k, kk = k >> 1, e = k & 1;
-    const int L = 8 * (kk & 7) + ((kk >> 3) & 7), i = 8 * j + (kk >> 6);
-    const float2 *Yf = Y + f * (long long)R * C;
-    float2 *Hf = Hl + f * (long long)R * C + e * 1536 + i * 64 + L;
-    float p = 0.f;
-    if (b == 0) {
-        for (int r = 0; r < R; ++r) Hf[(long long)r * C] = float2{0.f, 0.f};
-        p = 1.f;
-    } else {
-        const float2 x = X[b - 1];
-        for (int r = 0; r < R; ++r) {
-            const float2 h = ls_conj(Yf[(long long)r * C + b], x);
-            Hf[(long long)r * C] = h;
-            p = (r == 0) ? (h.x * h.x) + (h.y * h.y) : p + (h.x * h.x) + (h.y * h.y);
-        }
-    }
-    P[f * C + b] = p;
-}
+OFDM_K_LS(3072)
 
 }  // namespace td3072
 
@@ -377,14 +368,10 @@ __global__ void __launch_bounds__(256) k_ls_3072(const float2 *__restrict__ Y, i
 // estimate is [e][slot][lane] per row (k_ls_6144).
 namespace td6144 {
 
-using pk::v2f;
+using namespace lane512;
 constexpr int C = 6144, K = C - 1;
 constexpr int XS = 24 * 64;
 constexpr int NT = 256;  // one quad per workgroup
-
-__device__ __forceinline__ int bin_of(int e, int L, int i) {
-    return 3 * (4 * ((L >> 3) + 8 * (L & 7) + 64 * (i & 7)) + e) + (i >> 3);
-}
 
 __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2)))
 k_mrc_td6144(const float2 *__restrict__ iq, long long nframes, int S, int R, int prefix, const float2 *__restrict__ Hl,
@@ -399,19 +386,11 @@ k_mrc_td6144(const float2 *__restrict__ iq, long long nframes, int S, int R, int
     }
     const int e = threadIdx.x >> 6, L = threadIdx.x & 63;
     v2f twA[7], twB[7];
-#pragma unroll
-    for (int k = 1; k < 8; ++k) {
-        double sn, cs;
-        sincospi(-2.0 * (double)((L * k) % 512) / 512.0, &sn, &cs);
-        twA[k - 1] = v2f{(float)cs, (float)sn};
-        sincospi(-2.0 * (double)(((L & 7) * k) % 64) / 64.0, &sn, &cs);
-        twB[k - 1] = v2f{(float)cs, (float)sn};
-    }
+    row_twiddles<8>(L, twA, twB);
     __syncthreads();
     float2 *own = xch[e];
     const int nsd = S - 1;
     const long long Cp = C + prefix, nq = nframes * nsd, np = gridDim.x;
-    const float r3 = 0.86602540378443865f;
     auto row_ptr = [&](long long q, int r) {
         const long long f = q / nsd, s = 1 + q % nsd;
         return iq + ((f * S + s) * R + r) * Cp + prefix;
@@ -420,7 +399,7 @@ k_mrc_td6144(const float2 *__restrict__ iq, long long nframes, int S, int R, int
 #pragma unroll
         for (int i = 0; i < 3; ++i)
 #pragma unroll
-            for (int m = 0; m < 8; ++m) x[8 * i + m] = td1536::ld_stream(b + L + 64 * (m + 8 * e + 32 * i));
+            for (int m = 0; m < 8; ++m) x[8 * i + m] = ld_stream(b + L + 64 * (m + 8 * e + 32 * i));
     };
     float2 x[24];
     long long q = blockIdx.x;
@@ -432,17 +411,7 @@ k_mrc_td6144(const float2 *__restrict__ iq, long long nframes, int S, int R, int
         for (int i = 0; i < 24; ++i) acc[i] = v2f{0.f, 0.f};
         for (int r = 0; r < R; ++r) {
             v2f u[3][8];
-#pragma unroll
-            for (int m = 0; m < 8; ++m) {
-                const v2f a0 = pk::V(x[m]), a1 = pk::V(x[m + 8]), a2 = pk::V(x[m + 16]);
-                const v2f sm = a1 + a2, df = a1 - a2;
-                const v2f t0 = a0 - sm * (v2f){0.5f, 0.5f};
-                const v2f jd = v2f{df.y * r3, -df.x * r3};
-                const int n = L + 64 * (m + 8 * e);
-                u[0][m] = a0 + sm;
-                u[1][m] = pk::cmul(t0 + jd, pk::V(tab[n]));
-                u[2][m] = pk::cmul(t0 - jd, pk::V(tab[2 * n]));  // 2 n < 4096
-            }
+            radix3_dif(x, u, tab, L + 512 * e);  // 2 n < 4096
             {
                 const long long qn = r + 1 < R ? q : q + np;
                 if (qn < nq) load(x, row_ptr(qn, r + 1 < R ? r + 1 : 0));
@@ -475,55 +444,17 @@ k_mrc_td6144(const float2 *__restrict__ iq, long long nframes, int S, int R, int
                 v2f h[8];
 #pragma unroll
                 for (int d = 0; d < 8; ++d) h[d] = pk::V(hrow[(8 * j + d) * 64 + L]);
-                td1536::fft512(u[j], own, L, twA, twB);
+                fft512(u[j], own, L, twA, twB);
 #pragma unroll
                 for (int d = 0; d < 8; ++d) pk::mac(acc[8 * j + d], u[j][d], h[d]);
             }
         }
-        float2 *o = out + q * K;
-        const float *Pf = P + f * C;
-        // the lane recomputed here: output offsets hoisted out of the symbol
-        // loop were spilled and reloaded behind a vmcnt(0) that drained the
-        // next symbol's row load
-        const int Le = lane_here();
-#pragma unroll
-        for (int i = 0; i < 24; ++i) {
-            const int b = bin_of(e, Le, i);
-            if (b == 0) continue;
-            const float2 a = pk::F(acc[i]);
-            if (mode == 0) {
-                const float p = Pf[b];
-                o[out_pos(b - 1, K)] = float2{a.x * __builtin_amdgcn_rcpf(p), a.y * __builtin_amdgcn_rcpf(p)};
-            } else {
-                o[b - 1] = a;
-            }
-        }
+        const int Le = lane_here();  // not L: see store_symbol
+        store_symbol<C>(acc, [&](int i) { return lane::bin512(4, e, Le, i); }, P + f * C, out + q * K, mode);
     }
 }
 
-__global__ void __launch_bounds__(256) k_ls_6144(const float2 *__restrict__ Y, int R, const float2 *__restrict__ X,
-                                                 float2 *__restrict__ Hl, float *__restrict__ P) {
-    const int b = blockIdx.x * 256 + threadIdx.x;
-    if (b >= C) return;
-    const long long f = blockIdx.y;
-    const int k = b / 3, j = b - 3 * k, kk = k >> 2, e = k & 3;  // b = 3 (4 k' + e) + j
-    const int L = 8 * (kk & 7) + ((kk >> 3) & 7), i = 8 * j + (kk >> 6);
-    const float2 *Yf = Y + f * (long long)R * C;
-    float2 *Hf = Hl + f * (long long)R * C + e * 1536 + i * 64 + L;
-    float p = 0.f;
-    if (b == 0) {
-        for (int r = 0; r < R; ++r) Hf[(long long)r * C] = float2{0.f, 0.f};
-        p = 1.f;
-    } else {
-        const float2 x = X[b - 1];
-        for (int r = 0; r < R; ++r) {
-            const float2 h = ls_conj(Yf[(long long)r * C + b], x);
-            Hf[(long long)r * C] = h;
-            p = (r == 0) ? (h.x * h.x) + (h.y * h.y) : p + (h.x * h.x) + (h.y * h.y);
-        }
-    }
-    P[f * C + b] = p;
-}
+OFDM_K_LS(6144)
 
 }  // namespace td6144
 
@@ -536,10 +467,10 @@ __global__ void __launch_bounds__(256) k_ls_6144(const float2 *__restrict__ Y, i
 // so lane L = 8 (rho P + s') + c ends with bins s' + P c + 8 P d (slot d) of
 // row r0 + rho.  Each lane accumulates its rows rho, rho + NR, ...; the NR
 // partial sums meet once per symbol (lane xor 8 P, 16 P).  Estimate per row:
-// [slot d][lane mod 8 P] (k_ls_small).  Rows past R enter as zeros.
+// [slot d][lane mod 8 P] (lane::bin_small).  Rows past R enter as zeros.
 namespace tdsmall {
 
-using pk::v2f;
+using namespace lane512;
 constexpr int WAVES = 4, NT = 64 * WAVES;
 
 template <int NR>
@@ -547,22 +478,11 @@ __device__ __forceinline__ void mrc_small(const float2 *__restrict__ iq, long lo
                                           const float2 *__restrict__ Hl, const float *__restrict__ P,
                                           float2 *__restrict__ out, int mode) {
     constexpr int NP = 8 / NR, C = 64 * NP, K = C - 1, LW = 8 * NP;
-    __shared__ float2 img[WAVES][td1536::TS];
+    __shared__ float2 img[WAVES][TS];
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), L = threadIdx.x & 63, rho = L / LW, lw = L % LW;
     float2 *T = img[w];
     v2f twA[NP > 1 ? NP - 1 : 1], twB[7];
-#pragma unroll
-    for (int k = 1; k < NP; ++k) {
-        double sn, cs;
-        sincospi(-2.0 * (double)((L * k) % C) / (double)C, &sn, &cs);
-        twA[k - 1] = v2f{(float)cs, (float)sn};
-    }
-#pragma unroll
-    for (int k = 1; k < 8; ++k) {
-        double sn, cs;
-        sincospi(-2.0 * (double)(((L & 7) * k) % 64) / 64.0, &sn, &cs);
-        twB[k - 1] = v2f{(float)cs, (float)sn};
-    }
+    row_twiddles<NP>(L, twA, twB);
     const int nsd = S - 1;
     const long long Cp = C + prefix, nq = nframes * nsd, nw = (long long)gridDim.x * WAVES;
     float2 x[8];
@@ -574,7 +494,7 @@ __device__ __forceinline__ void mrc_small(const float2 *__restrict__ iq, long lo
 #pragma unroll
         for (int g = 0; g < NR; ++g)
 #pragma unroll
-            for (int m = 0; m < NP; ++m) x[g * NP + m] = r0 + g < R ? td1536::ld_stream(b + g * Cp + L + 64 * m) : float2{0.f, 0.f};
+            for (int m = 0; m < NP; ++m) x[g * NP + m] = r0 + g < R ? ld_stream(b + g * Cp + L + 64 * m) : float2{0.f, 0.f};
     };
     long long q = (long long)blockIdx.x * WAVES + w;
     if (q < nq) load(row_ptr(q), 0);
@@ -609,7 +529,7 @@ __device__ __forceinline__ void mrc_small(const float2 *__restrict__ iq, long lo
 #pragma unroll
                 for (int m = 0; m < NP; ++m) u[g * NP + m] = a[m];
             }
-            td1536::fft64x8(u, T, L, twB);
+            fft64x8(u, T, L, twB);
 #pragma unroll
             for (int d = 0; d < 8; ++d) pk::mac(acc[d], u[d], h[d]);
         }
@@ -621,47 +541,8 @@ __device__ __forceinline__ void mrc_small(const float2 *__restrict__ iq, long lo
                 acc[d] += v2f{__shfl_xor(a.x, o), __shfl_xor(a.y, o)};
             }
         if (rho != 0) continue;
-        float2 *o = out + q * K;
-        const float *Pf = P + f * C;
-#pragma unroll
-        for (int d = 0; d < 8; ++d) {
-            const int b = (lw >> 3) + NP * (lw & 7) + LW * d;
-            if (b == 0) continue;  // the DC bin carries no subcarrier
-            const float2 a = pk::F(acc[d]);
-            if (mode == 0) {
-                const float p = Pf[b];
-                o[out_pos(b - 1, K)] = float2{a.x * __builtin_amdgcn_rcpf(p), a.y * __builtin_amdgcn_rcpf(p)};
-            } else {
-                o[b - 1] = a;
-            }
-        }
+        store_symbol<C>(acc, [&](int d) { return lane::bin_small(NP, lw, d); }, P + f * C, out + q * K, mode);
     }
-}
-
-// LS from the FFT'd pilot rows into the lane order above (as k_ls_1536).
-template <int NR>
-__device__ __forceinline__ void ls_small(const float2 *__restrict__ Y, int R, const float2 *__restrict__ X,
-                                         float2 *__restrict__ Hl, float *__restrict__ P) {
-    constexpr int NP = 8 / NR, C = 64 * NP, LW = 8 * NP;
-    const int b = blockIdx.x * 256 + threadIdx.x;
-    if (b >= C) return;
-    const long long f = blockIdx.y;
-    const int pos = (b / LW) * LW + 8 * (b % NP) + ((b / NP) & 7);
-    const float2 *Yf = Y + f * (long long)R * C;
-    float2 *Hf = Hl + f * (long long)R * C + pos;
-    float p = 0.f;
-    if (b == 0) {
-        for (int r = 0; r < R; ++r) Hf[(long long)r * C] = float2{0.f, 0.f};
-        p = 1.f;
-    } else {
-        const float2 x = X[b - 1];
-        for (int r = 0; r < R; ++r) {
-            const float2 h = ls_conj(Yf[(long long)r * C + b], x);
-            Hf[(long long)r * C] = h;
-            p = (r == 0) ? (h.x * h.x) + (h.y * h.y) : p + (h.x * h.x) + (h.y * h.y);
-        }
-    }
-    P[f * C + b] = p;
 }
 
 #define OFDM_TD_SMALL(CC, NR)                                                                                          \
@@ -671,19 +552,48 @@ __device__ __forceinline__ void ls_small(const float2 *__restrict__ Y, int R, co
                                                        int mode) {                                                     \
         mrc_small<NR>(iq, nframes, S, R, prefix, Hl, P, out, mode);                                                    \
     }                                                                                                                  \
-    __global__ void __launch_bounds__(256) k_ls_##CC(const float2 *__restrict__ Y, int R,                              \
-                                                     const float2 *__restrict__ X, float2 *__restrict__ Hl,            \
-                                                     float *__restrict__ P) {                                          \
-        ls_small<NR>(Y, R, X, Hl, P);                                                                                  \
-    }
+    OFDM_K_LS(CC)
 OFDM_TD_SMALL(512, 1)
 OFDM_TD_SMALL(256, 2)
 OFDM_TD_SMALL(128, 4)
 #undef OFDM_TD_SMALL
+#undef OFDM_K_LS
 
 }  // namespace tdsmall
 
 namespace {
+
+using LsKern = void (*)(const float2 *, int, const float2 *, float2 *, float *);
+using MrcKern = void (*)(const float2 *, long long, int, int, int, const float2 *, const float *, float2 *, int);
+
+// The family: each size's kernels, the MRC workgroup (threads), the resident
+// workgroups per CU it is sized for and the data symbols a workgroup owns at
+// a time.
+const struct Lane512 {
+    int C;
+    LsKern ls;
+    MrcKern mrc;
+    int nt, per_cu, per_wg;
+} kLane512[] = {
+    // 4 one-wave symbols per workgroup, 4 workgroups per CU
+    {128, tdsmall::k_ls_128, tdsmall::k_mrc_td128, tdsmall::NT, 4, tdsmall::WAVES},
+    {256, tdsmall::k_ls_256, tdsmall::k_mrc_td256, tdsmall::NT, 4, tdsmall::WAVES},
+    {512, tdsmall::k_ls_512, tdsmall::k_mrc_td512, tdsmall::NT, 4, tdsmall::WAVES},
+    // 4 one-wave symbols per workgroup, 2 workgroups per CU (2 waves / SIMD)
+    {1536, td1536::k_ls_1536, td1536::k_mrc_td1536, td1536::NT, 2, td1536::WAVES},
+    // one wave pair (40 KiB of LDS) per workgroup, 4 per CU
+    {3072, td3072::k_ls_3072, td3072::k_mrc_td3072, td3072::NT, 4, 1},
+    // one wave quad (80 KiB of static LDS: the 32 KiB twiddle table and four
+    // 12 KiB exchange images) per workgroup, 2 per CU (static_assert in
+    // k_mrc_td6144; the occupancy query in launch_mrc_lane512 has the last word)
+    {6144, td6144::k_ls_6144, td6144::k_mrc_td6144, td6144::NT, 2, 1},
+};
+
+const Lane512 *lane512_row(int C) {
+    for (const Lane512 &k : kLane512)
+        if (k.C == C) return &k;
+    return nullptr;
+}
 
 int cu_count() {
     int dev = 0, cus = 256;
@@ -692,93 +602,44 @@ int cu_count() {
     return cus;
 }
 
+}  // namespace
+
+bool lane512_supported(int C) { return lane512_row(C) != nullptr; }
+
 // One workgroup column per 256 bins, one grid row per frame (65535 at a time).
-template <int CC, typename Kern>
-hipError_t launch_ls_lane(Kern kern, const float2 *Y, long long nframes, int R, const float2 *X, float2 *Hl, float *P,
-                          hipStream_t s) {
+hipError_t launch_ls_lane512(int C, const float2 *Y, long long nframes, int R, const float2 *X, float2 *Hl, float *P,
+                             hipStream_t s) {
+    const Lane512 *k = lane512_row(C);
+    if (!k) return hipErrorInvalidValue;
     if (nframes <= 0) return hipSuccess;
     for (long long f0 = 0; f0 < nframes; f0 += 65535) {
         const long long n = nframes - f0 < 65535 ? nframes - f0 : 65535;
-        hipLaunchKernelGGL(kern, dim3((CC + 255) / 256, (unsigned)n), dim3(256), 0, s, Y + f0 * (long long)R * CC, R,
-                           X, Hl + f0 * (long long)R * CC, P + f0 * CC);
+        hipLaunchKernelGGL(k->ls, dim3((C + 255) / 256, (unsigned)n), dim3(256), 0, s, Y + f0 * (long long)R * C, R, X,
+                           Hl + f0 * (long long)R * C, P + f0 * C);
     }
     return hipGetLastError();
 }
 
 // Persistent grid: min(workgroups needed, per_cu x CUs); each workgroup owns
 // `per_wg` data symbols at a time.
-template <typename Kern>
-hipError_t launch_mrc_lane(Kern kern, int nt, int per_cu, int per_wg, const float2 *iq, long long nframes, int S,
-                           int R, int prefix, const float2 *Hl, const float *P, float2 *out, int mode, hipStream_t s) {
+hipError_t launch_mrc_lane512(int C, const float2 *iq, long long nframes, int S, int R, int prefix, const float2 *Hl,
+                              const float *P, float2 *out, int mode, hipStream_t s) {
+    const Lane512 *k = lane512_row(C);
+    if (!k) return hipErrorInvalidValue;
     const long long nq = nframes * (S - 1);
     if (nq <= 0) return hipSuccess;
     // the resident count from the occupancy query (LDS, registers), capped by
     // the hint: a kernel that outgrows its LDS budget shrinks the grid
     // instead of queueing workgroups behind a persistent one
-    int occ = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, reinterpret_cast<const void *>(kern), nt, 0) ==
+    int occ = 0, per_cu = k->per_cu;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, reinterpret_cast<const void *>(k->mrc), k->nt, 0) ==
             hipSuccess &&
         occ > 0 && occ < per_cu)
         per_cu = occ;
-    const long long res = (long long)per_cu * cu_count(), need = (nq + per_wg - 1) / per_wg;
-    hipLaunchKernelGGL(kern, dim3((unsigned)(need < res ? need : res)), dim3(nt), 0, s, iq, nframes, S, R, prefix, Hl,
-                       P, out, mode);
+    const long long res = (long long)per_cu * cu_count(), need = (nq + k->per_wg - 1) / k->per_wg;
+    hipLaunchKernelGGL(k->mrc, dim3((unsigned)(need < res ? need : res)), dim3(k->nt), 0, s, iq, nframes, S, R, prefix,
+                       Hl, P, out, mode);
     return hipGetLastError();
-}
-
-}  // namespace
-
-hipError_t launch_ls_small(int C, const float2 *Y, long long nframes, int R, const float2 *X, float2 *Hl, float *P,
-                           hipStream_t s) {
-    return C == 512   ? launch_ls_lane<512>(tdsmall::k_ls_512, Y, nframes, R, X, Hl, P, s)
-           : C == 256 ? launch_ls_lane<256>(tdsmall::k_ls_256, Y, nframes, R, X, Hl, P, s)
-           : C == 128 ? launch_ls_lane<128>(tdsmall::k_ls_128, Y, nframes, R, X, Hl, P, s)
-                      : hipErrorInvalidValue;
-}
-
-hipError_t launch_ls_1536(const float2 *Y, long long nframes, int R, const float2 *X, float2 *Hl, float *P,
-                          hipStream_t s) {
-    return launch_ls_lane<td1536::C>(td1536::k_ls_1536, Y, nframes, R, X, Hl, P, s);
-}
-
-hipError_t launch_ls_3072(const float2 *Y, long long nframes, int R, const float2 *X, float2 *Hl, float *P,
-                          hipStream_t s) {
-    return launch_ls_lane<td3072::C>(td3072::k_ls_3072, Y, nframes, R, X, Hl, P, s);
-}
-
-hipError_t launch_ls_6144(const float2 *Y, long long nframes, int R, const float2 *X, float2 *Hl, float *P,
-                          hipStream_t s) {
-    return launch_ls_lane<td6144::C>(td6144::k_ls_6144, Y, nframes, R, X, Hl, P, s);
-}
-
-// 512 / 256 / 128: 4 one-wave symbols per workgroup, 4 workgroups per CU.
-hipError_t launch_mrc_small(int C, const float2 *iq, long long nframes, int S, int R, int prefix, const float2 *Hl,
-                            const float *P, float2 *out, int mode, hipStream_t s) {
-    using namespace tdsmall;
-    auto kern = C == 512 ? k_mrc_td512 : C == 256 ? k_mrc_td256 : C == 128 ? k_mrc_td128 : nullptr;
-    if (!kern) return hipErrorInvalidValue;
-    return launch_mrc_lane(kern, NT, 4, WAVES, iq, nframes, S, R, prefix, Hl, P, out, mode, s);
-}
-
-// 1536: 4 one-wave symbols per workgroup, 2 workgroups per CU (2 waves / SIMD).
-hipError_t launch_mrc_td1536(const float2 *iq, long long nframes, int S, int R, int prefix, const float2 *Hl,
-                             const float *P, float2 *out, int mode, hipStream_t s) {
-    return launch_mrc_lane(td1536::k_mrc_td1536, td1536::NT, 2, td1536::WAVES, iq, nframes, S, R, prefix, Hl, P, out,
-                           mode, s);
-}
-
-// 3072: one wave pair (40 KiB of LDS) per workgroup, 4 per CU.
-hipError_t launch_mrc_td3072(const float2 *iq, long long nframes, int S, int R, int prefix, const float2 *Hl,
-                             const float *P, float2 *out, int mode, hipStream_t s) {
-    return launch_mrc_lane(td3072::k_mrc_td3072, td3072::NT, 4, 1, iq, nframes, S, R, prefix, Hl, P, out, mode, s);
-}
-
-// 6144: one wave quad (80 KiB of static LDS: the 32 KiB twiddle table and
-// four 12 KiB exchange images) per workgroup, 2 per CU (static_assert in
-// k_mrc_td6144; the occupancy query in launch_mrc_lane has the last word).
-hipError_t launch_mrc_td6144(const float2 *iq, long long nframes, int S, int R, int prefix, const float2 *Hl,
-                             const float *P, float2 *out, int mode, hipStream_t s) {
-    return launch_mrc_lane(td6144::k_mrc_td6144, td6144::NT, 2, 1, iq, nframes, S, R, prefix, Hl, P, out, mode, s);
 }
 
 }  // namespace ofdm

@@ -67,28 +67,15 @@ hipError_t launch_fft_any_b(const float2 *in, long long in_stride, long long in_
                             int in_off, float2 *out, long long out_stride, int out_off, long long nrows, int C,
                             bool inverse, float scale, hipStream_t s);
 bool fft_any_supported(int C);
-// C = 1536 (frame_td_fft512.hip): LS from FFT'd pilot rows (staging, frame
-// stride R*C) into the lane-order Hc + bin-layout P, and the fused MRC.
-hipError_t launch_ls_1536(const float2 *Y, long long nframes, int R, const float2 *X, float2 *Hl, float *P,
-                          hipStream_t s);
-hipError_t launch_mrc_td1536(const float2 *iq, long long nframes, int S, int R, int prefix, const float2 *Hl,
-                             const float *P, float2 *out, int mode, hipStream_t s);
-// ... and C = 3072 on a wave pair per symbol (same file)
-hipError_t launch_ls_3072(const float2 *Y, long long nframes, int R, const float2 *X, float2 *Hl, float *P,
-                          hipStream_t s);
-hipError_t launch_mrc_td3072(const float2 *iq, long long nframes, int S, int R, int prefix, const float2 *Hl,
-                             const float *P, float2 *out, int mode, hipStream_t s);
-// ... C = 512 / 256 / 128 on one wave per symbol (same file; other C:
-// hipErrorInvalidValue)
-hipError_t launch_ls_small(int C, const float2 *Y, long long nframes, int R, const float2 *X, float2 *Hl, float *P,
-                           hipStream_t s);
-hipError_t launch_mrc_small(int C, const float2 *iq, long long nframes, int S, int R, int prefix, const float2 *Hl,
-                            const float *P, float2 *out, int mode, hipStream_t s);
-// ... and C = 6144 on a wave quad per symbol (same file)
-hipError_t launch_ls_6144(const float2 *Y, long long nframes, int R, const float2 *X, float2 *Hl, float *P,
-                          hipStream_t s);
-hipError_t launch_mrc_td6144(const float2 *iq, long long nframes, int S, int R, int prefix, const float2 *Hl,
-                             const float *P, float2 *out, int mode, hipStream_t s);
+// The FFT512 family (frame_td_fft512.hip: C = 128, 256, 512, 1536 on one wave
+// per symbol, 3072 on a pair, 6144 on a quad): LS from FFT'd pilot rows
+// (staging, frame stride R*C) into the lane-order Hc (lane_layout.hpp) +
+// bin-layout P, and the fused MRC.  Other C: hipErrorInvalidValue.
+bool lane512_supported(int C);
+hipError_t launch_ls_lane512(int C, const float2 *Y, long long nframes, int R, const float2 *X, float2 *Hl, float *P,
+                             hipStream_t s);
+hipError_t launch_mrc_lane512(int C, const float2 *iq, long long nframes, int S, int R, int prefix, const float2 *Hl,
+                              const float *P, float2 *out, int mode, hipStream_t s);
 // Fused any-C MRC (fft_any.hip k_mrc_any): data symbols of frames
 // iq + f*S*R*(C+prefix) (symbols 1..S-1) against the staged estimate in the
 // bin layout (Hc [F][R][C], P [F][C]); mode 0: out[q][out_pos_any(j)] =

@@ -17,6 +17,7 @@
 //                    [R][K], Hsqrd [K] -- what demodOneFrameCUDA leaves in its
 //                    Hconj / Hsqrd arguments (gpuLS.cu:617-629)
 #include "common.hpp"
+#include "lane_layout.hpp"
 #include "launch.hpp"
 
 namespace ofdm {
@@ -62,48 +63,8 @@ __global__ void __launch_bounds__(256) k_dist_sqrd(const float2 *__restrict__ H,
     P[j] = p;
 }
 
-// Position of bin b (1 <= b < C) inside one lane-ordered Hc row of C float2
-// (frame_td.hip / frame_td2048.hip / frame_td4096.hip: lane t of a wave owns
-// the bins b0(t) + 16 k, b0(t) = (t >> 2) + 256 c(t & 3), c(a) = (a >> 1) + 2 (a & 1)).
-// Other C: bin layout (position = b).
-__device__ __forceinline__ int lane_of(int b, int &k) {  // b < 1024
-    const int q = b & 15, c = b >> 8;
-    k = (b >> 4) & 15;
-    return 4 * q + (((c & 1) << 1) | (c >> 1));
-}
-__device__ __forceinline__ int hc_pos(int b, int C) {  // C = 0: bin layout
-    int k;
-    if (C == 1024) {  // float4 (k >> 1) * 64 + t holds bins (k & ~1, k | 1) of lane t
-        const int t = lane_of(b, k);
-        return 2 * ((k >> 1) * 64 + t) + (k & 1);
-    }
-    if (C == 2048) {  // float4 k * 64 + t = (Hc[2 b'], Hc[2 b' + 1]), b' = b0(t) + 16 k
-        const int t = lane_of(b >> 1, k);
-        return 2 * (k * 64 + t) + (b & 1);
-    }
-    if (C == 1536) {  // frame_td_fft512.hip: slot 8 j + d of lane 8 s + c holds bin 3 (s + 8 c + 64 d) + j
-        const int q = b / 3, j = b - 3 * q;
-        return (8 * j + (q >> 6)) * 64 + 8 * (q & 7) + ((q >> 3) & 7);
-    }
-    if (C == 3072) {  // wave e, slot 8 j + d of lane 8 s + c holds bin 3 (2 (s + 8 c + 64 d) + e) + j
-        const int q = b / 3, j = b - 3 * q, e = q & 1, kk = q >> 1;
-        return e * 1536 + (8 * j + (kk >> 6)) * 64 + 8 * (kk & 7) + ((kk >> 3) & 7);
-    }
-    if (C == 512 || C == 256 || C == 128) {  // P = C / 64: slot d of lane 8 s + c holds bin s + P c + 8 P d
-        const int np = C >> 6, lw = 8 * np;
-        return (b / lw) * lw + 8 * (b % np) + ((b / np) & 7);
-    }
-    if (C == 6144) {  // wave e, slot 8 j + d of lane 8 s + c holds bin 3 (4 (s + 8 c + 64 d) + e) + j
-        const int q = b / 3, j = b - 3 * q, e = q & 3, kk = q >> 2;
-        return e * 1536 + (8 * j + (kk >> 6)) * 64 + 8 * (kk & 7) + ((kk >> 3) & 7);
-    }
-    if (C == 4096) {  // float2 e * 2048 + h * 1024 + (k >> 1) * 128 + 2 t + (k & 1) = Hc[4 b' + 2 h + e]
-        const int t = lane_of(b >> 2, k);
-        return (b & 1) * 2048 + ((b >> 1) & 1) * 1024 + (k >> 1) * 128 + 2 * t + (k & 1);
-    }
-    return b;
-}
-
+// One frame's estimate out of the workspace: Hc rows in the lane order of
+// C's receiver (lane_layout.hpp; lay = C) or in bin layout (lay = 0).
 __global__ void __launch_bounds__(256) k_export_estimate(const float2 *__restrict__ Hc,
                                                          const float *__restrict__ P, int R, int C,
                                                          int lay, float2 *__restrict__ Hconj,
@@ -111,7 +72,7 @@ __global__ void __launch_bounds__(256) k_export_estimate(const float2 *__restric
     const int K = C - 1;
     const int r = blockIdx.y;
     for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < K; j += gridDim.x * blockDim.x) {
-        Hconj[(long long)r * K + j] = Hc[(long long)r * C + hc_pos(j + 1, lay)];
+        Hconj[(long long)r * K + j] = Hc[(long long)r * C + lane::hc_pos(lay, j + 1)];
         if (r == 0 && Hsqrd) Hsqrd[j] = P[j + 1];
     }
 }
