@@ -949,4 +949,24 @@ int ofdm_zf_detect_ex(const ofdm_cf32 *d_Wt, const ofdm_cf32 *d_Y, long long ldy
                      fn);
 }
 
+int ofdm_tx_modulate(const ofdm_cf32 *d_X, long long ldx, long long nrows, int C, int cp_len, int map, int norm,
+                     float scale, ofdm_cf32 *d_iq, float *d_peak, ofdm_stream_t stream) {
+    static const char *fn = "ofdm_tx_modulate";
+    if (!valid_c(C)) return fail(OFDM_E_ARG, "%s: C=%d out of [2, %d]", fn, C, ofdm::FFT_ANY_MAX);
+    if (cp_len < 0 || cp_len > C) return fail(OFDM_E_ARG, "%s: cp_len=%d outside [0, C=%d]", fn, cp_len, C);
+    if (nrows < 0) return fail(OFDM_E_ARG, "%s: nrows < 0", fn);
+    if (ldx < C - 1) return fail(OFDM_E_ARG, "%s: ldx=%lld below K=%d", fn, ldx, C - 1);
+    if (map != OFDM_TX_MAP_REFERENCE && map != OFDM_TX_MAP_RX)
+        return fail(OFDM_E_ARG, "%s: map=%d is neither OFDM_TX_MAP_REFERENCE nor OFDM_TX_MAP_RX", fn, map);
+    if (norm != OFDM_TX_NORM_PEAK && norm != OFDM_TX_NORM_SCALE)
+        return fail(OFDM_E_ARG, "%s: norm=%d is neither OFDM_TX_NORM_PEAK nor OFDM_TX_NORM_SCALE", fn, norm);
+    if (nrows == 0) return OFDM_OK;
+    if (!d_X || !d_iq) return fail(OFDM_E_ARG, "%s: null pointer", fn);
+    if (!aligned(d_X, 8) || !aligned(d_iq, 8) || !aligned(d_peak, 4))
+        return fail(OFDM_E_ARG, "%s: d_X and d_iq must be 8-B aligned, d_peak 4-B", fn);
+    return hip_check(ofdm::launch_tx_modulate(F2(d_X), ldx, nrows, C, cp_len, map, norm, scale, F2(d_iq), d_peak,
+                                              hs(stream)),
+                     fn);
+}
+
 }  // extern "C"

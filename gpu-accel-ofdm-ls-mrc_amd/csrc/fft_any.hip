@@ -1,6 +1,8 @@
 // fft_any.hip -- FFT lengths beyond the fused receivers: a batched row FFT of
 // ANY length C in [2, 8192] (k_fft_any) and the fused any-C MRC (k_mrc_any:
-// FFT + combine + normalise + rotate in one HBM pass), for the sizes the
+// FFT + combine + normalise + rotate in one HBM pass) and the any-C OFDM
+// modulator (k_tx_any: bin placement + backward FFT + peak + scale + cyclic
+// prefix in one HBM pass; ofdm_tx_modulate), for the sizes the
 // power-of-two kernels (k_fft_rows, the fused C = 1024 / 2048 / 4096
 // receivers) do not cover: 1536 (LTE 15 MHz), 3072, 6144, 600, 1200, odd and
 // prime lengths, 8192 and the small powers of two.  The reference transforms
@@ -34,6 +36,7 @@
 #include "common.hpp"
 #include "launch.hpp"
 #include "pk.hpp"
+#include "tx_map.hpp"
 
 namespace ofdm {
 namespace fany {
@@ -293,6 +296,68 @@ k_fft_any(const float2 *__restrict__ in, long long in_stride, long long in_rb, l
             dst[g * out_stride + (e - g * C)] = float2{v.x * scale, v.y * scale};
         }
         lds_sync();  // the next group's rows go into x0
+    }
+}
+
+// OFDM modulator for any C (ofdm_tx_modulate; C = 1024 has its own wave
+// kernel, tx_mod.hip): one workgroup per row.  The row's K inputs go through
+// the inverse of the bin placement (tx_map.hpp) into x0, the plan's stages run
+// backward, the peak max_n |x[n]|^2 is taken by a fixed LDS tree, and the row
+// is stored once, scaled, behind its cyclic prefix (addPrefix,
+// cpuLS.hpp:391-398): K * 8 B read and (C + cp) * 8 B written per row.
+template <int CAP, int NT = nt_of(CAP)>
+__global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(wpe_of(CAP), wpe_of(CAP))))
+k_tx_any(const float2 *__restrict__ X, long long ldx, long long nrows, int cp, int map, int norm, float scale,
+         float2 *__restrict__ iq, float *__restrict__ peak, Plan plan) {
+    constexpr int MAXE = CAP / NT;
+    __shared__ float2 x0[CAP], x1[CAP], lo[TLO], hi[THI];
+    __shared__ float red[NT];
+    const unsigned C = (unsigned)plan.C, Cp = C + (unsigned)cp;
+    fill_tables<NT>(lo, hi, C);
+    const Tw T{lo, hi};
+    // bins t + i NT of a row, through the placement map, into registers: in
+    // flight while the previous row's stages run (as k_fft_any's row groups)
+    unsigned long long pf[MAXE];
+    auto load_row = [&](long long row) {
+        const unsigned long long *src = reinterpret_cast<const unsigned long long *>(X + row * ldx);
+#pragma unroll
+        for (int i = 0; i < MAXE; ++i) {
+            const unsigned b = tid_here() + i * NT;
+            const int k = b < C ? tx_src((int)b, (int)C, map) : -1;
+            pf[i] = 0;
+            if (k >= 0) pf[i] = __builtin_nontemporal_load(src + k);
+        }
+    };
+    if ((long long)blockIdx.x < nrows) load_row(blockIdx.x);
+    for (long long row = blockIdx.x; row < nrows; row += gridDim.x) {
+#pragma unroll
+        for (int i = 0; i < MAXE; ++i) x0[tid_here() + i * NT] = __builtin_bit_cast(float2, pf[i]);
+        lds_sync();  // the row and, the first time, the twiddle tables
+        if (row + gridDim.x < nrows) load_row(row + gridDim.x);
+        const float2 *res = run_stages<NT, true>(x0, x1, T, plan, 1, plan.ns);
+        float m2 = 0.f;
+        for (unsigned n = tid_here(); n < C; n += NT) {
+            const float2 v = res[n];
+            m2 = tx_max(m2, v.x * v.x + v.y * v.y);
+        }
+        red[tid_here()] = m2;
+        lds_sync();
+#pragma unroll 1
+        for (unsigned h = NT / 2; h >= 1; h >>= 1) {
+            const unsigned t = tid_here();
+            if (t < h) red[t] = tx_max(red[t], red[t + h]);
+            lds_sync();
+        }
+        const float pk = __builtin_sqrtf(red[0]);
+        const float s = tx_gain(pk, norm, scale);
+        float2 *o = iq + row * Cp;
+        for (unsigned e = tid_here(); e < Cp; e += NT) {
+            const float2 v = res[e < (unsigned)cp ? e + C - (unsigned)cp : e - (unsigned)cp];
+            __builtin_nontemporal_store(__builtin_bit_cast(unsigned long long, float2{v.x * s, v.y * s}),
+                                        reinterpret_cast<unsigned long long *>(o + e));
+        }
+        if (peak && tid_here() == 0) peak[row] = pk;
+        lds_sync();  // the next row goes into x0, its maxima into red
     }
 }
 
@@ -569,6 +634,16 @@ hipError_t launch_t(const float2 *in, long long in_stride, long long in_rb, long
 }
 
 template <int CAP>
+hipError_t launch_tx_t(const float2 *X, long long ldx, long long nrows, int cp, int map, int norm, float scale,
+                       float2 *iq, float *peak, const Plan &pl, hipStream_t s) {
+    const long long res = resident(CAP);
+    const unsigned grid = (unsigned)(nrows < res ? nrows : res);  // persistent over the rows
+    hipLaunchKernelGGL((k_tx_any<CAP>), dim3(grid), dim3(nt_of(CAP)), 0, s, X, ldx, nrows, cp, map, norm, scale, iq,
+                       peak, pl);
+    return hipGetLastError();
+}
+
+template <int CAP>
 hipError_t launch_mrc_t(const float2 *iq, long long nframes, int S, int R, int prefix, const float2 *Hc,
                         const float *P, float2 *out, int mode, const Plan &pl, hipStream_t s) {
     const long long nq = nframes * (S - 1);
@@ -606,6 +681,18 @@ hipError_t launch_fft_any(const float2 *in, long long in_stride, int in_off, flo
                           int out_off, long long nrows, int C, bool inverse, float scale, hipStream_t s) {
     return launch_fft_any_b(in, in_stride, nrows > 0 ? nrows : 1, 0, in_off, out, out_stride, out_off, nrows, C,
                             inverse, scale, s);
+}
+
+hipError_t launch_tx_any(const float2 *X, long long ldx, long long nrows, int C, int cp, int map, int norm,
+                         float scale, float2 *iq, float *peak, hipStream_t s) {
+    if (nrows <= 0) return hipSuccess;
+    fany::Plan pl;
+    if (!fany::make_plan(C, pl)) return hipErrorInvalidValue;
+    switch (fany::cap_of(C)) {
+    case 2048: return fany::launch_tx_t<2048>(X, ldx, nrows, cp, map, norm, scale, iq, peak, pl, s);
+    case 4096: return fany::launch_tx_t<4096>(X, ldx, nrows, cp, map, norm, scale, iq, peak, pl, s);
+    default: return fany::launch_tx_t<8192>(X, ldx, nrows, cp, map, norm, scale, iq, peak, pl, s);
+    }
 }
 
 hipError_t launch_mrc_any(const float2 *iq, long long nframes, int S, int R, int C, int prefix, const float2 *Hc,

@@ -174,6 +174,16 @@ hipError_t launch_noise_estimate(const float2 *z, long long nframes, int S, int 
 hipError_t launch_soft_demap(const float2 *z, long long nframes, int S, int C, const float *P, const float *nv,
                              int bps, int fmt, float llr_scale, void *out, hipStream_t s);
 
+// OFDM modulator (tx_mod.hip; any C but 1024: fft_any.hip k_tx_any): row i =
+// X + i*ldx (K values, through the bin placement `map`) -> backward FFT ->
+// iq + i*(C+cp): the last cp samples, then the C samples, times 1/peak
+// (norm 0) or scale (norm 1); peak[i] = max_n |x[n]| before scaling (may be
+// null).  2 <= C <= FFT_ANY_MAX, 0 <= cp <= C, ldx >= C - 1.
+hipError_t launch_tx_modulate(const float2 *X, long long ldx, long long nrows, int C, int cp, int map, int norm,
+                              float scale, float2 *iq, float *peak, hipStream_t s);
+hipError_t launch_tx_any(const float2 *X, long long ldx, long long nrows, int C, int cp, int map, int norm,
+                         float scale, float2 *iq, float *peak, hipStream_t s);
+
 // Synthetic frames: time-domain (freq_domain=0, rows of C+prefix with a
 // cyclic prefix) or frequency-domain (freq_domain=1, rows of C) IQ.
 hipError_t launch_synth(float2 *iq, long long nframes, int S, int R, int C, int prefix,

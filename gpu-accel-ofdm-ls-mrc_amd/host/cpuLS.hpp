@@ -19,10 +19,18 @@
 //   * the FFT plan is not rebuilt per row and doOneSymbol does not leak.
 // The multi-user zero-forcing helpers (rotCube, createZeroForcingMatrix,
 // multiplyWithChannelInv; cpuLS.hpp:400-463) are provided, computed by the
-// library's ZF kernels.  The remaining TX-side
-// helpers (ifftShiftOneRow, addPrefix, modRefSymbol, modOneSymbol;
-// cpuLS.hpp:119-132, 391-398, 466-529) are not part of the receiver path and
-// are not provided.
+// library's ZF kernels.  The TX-side helpers
+// (ifftShiftOneRow, addPrefix, modRefSymbol, modOneSymbol; cpuLS.hpp:119-132,
+// 391-398, 466-529) are provided too: the two modulators are one
+// ofdm_tx_modulate launch each (bin placement, backward FFT, peak
+// normalisation and prefix in one pass, OFDM_TX_MAP_REFERENCE +
+// OFDM_TX_NORM_PEAK); ifftShiftOneRow and addPrefix are the layout
+// permutations they are in the reference.  Where the reference's code defeats
+// its intent there as well:
+//   * modOneSymbol(chanMultiply = true) hands multiplyWithChannelInv the
+//     operands in the intended order (HX = Y, X, H); the reference passes
+//     (Y, H, X), the precoder where the symbols belong (cpuLS.hpp:494);
+//   * an all-zero row is modulated to zeros, not to NaN (0 * 1/0).
 #ifndef _CPULS_HPP_
 #define _CPULS_HPP_
 
@@ -180,6 +188,49 @@ inline void createZeroForcingMatrix(complexF *H, complexF *X, int rows, int cols
 inline void multiplyWithChannelInv(complexF *HX, complexF *X, complexF *H, int rows, int cols,
                                    int users) {
     ofdm::HostEngine::get().zf_apply(H, X, users, rows, cols - 1, HX);
+}
+
+// ifftShiftOneRow (cpuLS.hpp:119-132): swaps the two halves of cols / 2
+// elements of row `row` (for odd cols the last element stays); a layout
+// permutation, no arithmetic.
+inline void ifftShiftOneRow(complexF *Y, int cols, int row) {
+    complexF *Yf = &Y[(size_t)row * cols];
+    std::swap_ranges(Yf, Yf + cols / 2, Yf + cols / 2);
+}
+
+// addPrefix (cpuLS.hpp:391-398): Y[row] = the last `prefix` samples of
+// dY[row], then its cols samples (`prefix` is the ring header's macro).
+inline void addPrefix(complexF *Y, complexF *dY, int rows, int cols) {
+    for (int row = 0; row < rows; row++) {
+        complexF *y = &Y[(size_t)row * (cols + prefix)];
+        const complexF *d = &dY[(size_t)row * cols];
+        std::memcpy(y, d + (cols - prefix), (size_t)(prefix) * sizeof(*d));
+        std::memcpy(y + prefix, d, (size_t)cols * sizeof(*d));
+    }
+}
+
+// modRefSymbol (cpuLS.hpp:466-489): the rotated pilots (matrix_readX, left in
+// X) modulated as one row -> Y, cols + prefix samples of peak magnitude 1.
+inline void modRefSymbol(complexF *Y, complexF *X, int cols) {
+    matrix_readX(X, cols - 1);
+    ofdm::HostEngine::get().tx_modulate(X, 1, cols, prefix, OFDM_TX_MAP_REFERENCE, OFDM_TX_NORM_PEAK, 1.f, Y);
+}
+
+// modOneSymbol (cpuLS.hpp:492-529): the users' rows X (users x (cols-1)) --
+// or, with chanMultiply, their zero-forcing precoded antenna rows
+// multiplyWithChannelInv(Y, X, H) (rows x (cols-1), staged in Y as in the
+// reference; the reference swaps H and X in that call, cpuLS.hpp:494, the
+// intended order is used here) -- modulated row by row into Y, `rows` (resp.
+// `users`) rows of cols + prefix samples, each of peak magnitude 1.
+inline void modOneSymbol(complexF *Y, complexF *H, complexF *X, int rows, int cols, int users,
+                         bool chanMultiply = false) {
+    if (chanMultiply) {
+        multiplyWithChannelInv(Y, X, H, rows, cols, users);
+    } else {
+        rows = users;
+        std::memcpy(Y, X, (size_t)rows * (cols - 1) * sizeof(*X));
+    }
+    ofdm::HostEngine::get().tx_modulate(Y, rows, cols, prefix, OFDM_TX_MAP_REFERENCE, OFDM_TX_NORM_PEAK, 1.f, Y);
 }
 
 #endif  // _CPULS_HPP_

@@ -180,6 +180,17 @@ class HostEngine {
         check(ofdm_zf_apply(dWt, dX, U, R, K, 1, dY, s_), "ofdm_zf_apply");
         down(Y, dY, (size_t)R * K * 8);
     }
+    // OFDM modulator: nrows host rows of K = C - 1 values -> nrows host rows of
+    // C + cp samples (prefix first), in place allowed (X == iq: modOneSymbol
+    // stages its rows in its output buffer)
+    void tx_modulate(const void *X, int nrows, int C, int cp, int map, int norm, float scale, void *iq) {
+        const size_t bi = (size_t)nrows * (C - 1) * 8, bo = (size_t)nrows * (C + cp) * 8;
+        auto *dX = a_.get<ofdm_cf32>(bi);
+        auto *dY = b_.get<ofdm_cf32>(bo);
+        up(dX, X, bi);
+        check(ofdm_tx_modulate(dX, C - 1, nrows, C, cp, map, norm, scale, dY, nullptr, s_), "ofdm_tx_modulate");
+        down(iq, dY, bo);
+    }
 
   private:
     HostEngine() { hcheck(hipStreamCreate(&s_), "hipStreamCreate"); }

@@ -10,6 +10,7 @@ Mirrors the reference's operator surface:
   multiplyWithChannelConj + combineForMRC + shiftOneRow -> mrc_demod
   demodOneFrameCUDA (batched)      -> frame_demod / frame_demod_freq
   matrix_readX                     -> read_pilots / pilot_rotate
+  modOneSymbol / modRefSymbol      -> tx_modulate
 """
 import ctypes
 import os
@@ -80,6 +81,7 @@ _SIGS = {
     "ofdm_zf_detect": (_I, [_P, _P, _I, _I, _I, _LL, _P, _P]),
     "ofdm_zf_detect_ex": (_I, [_P, _P, _LL, _I, _I, _I, _LL, _P, _LL, _P]),
     "ofdm_zf_apply_ex": (_I, [_P, _P, _LL, _I, _I, _I, _LL, _P, _LL, _P]),
+    "ofdm_tx_modulate": (_I, [_P, _LL, _LL, _I, _I, _I, _I, _c.c_float, _P, _P, _P]),
     "ofdm_hbm_probe": (_I, [_I, _P, _P, _c.c_size_t, _c.c_size_t, _P]),
     "ofdm_device_status": (_I, []),
     "ofdm_device_status_inject": (_I, [_c.c_uint]),
@@ -621,6 +623,36 @@ def zf_detect_pitched(Wt, Y, out=None, ldx=None, stream=None):
     _check(lib().ofdm_zf_detect_ex(_dptr(Wt, "Wt"), _dptr(Y, "Y"), ldy, U, R, K, n, _dptr(out, "out"),
                                    out.shape[2], _stream(stream)), "ofdm_zf_detect_ex")
     return out
+
+
+TX_MAPS = {"reference": 0, "rx": 1}  # OFDM_TX_MAP_*
+TX_NORMS = {"peak": 0, "scale": 1}  # OFDM_TX_NORM_*
+
+
+def tx_modulate(X, C, cp=0, map="rx", norm="scale", scale=1.0, ldx=None, return_peak=False, out=None, stream=None):
+    """OFDM modulator (modOneSymbol / modRefSymbol, cpuLS.hpp:466-529, one pass
+    per row): X (..., ldx) device complex64, the first K = C - 1 values of
+    every row used (ldx default: X's last dimension) -> iq (..., C + cp), each
+    row's cyclic prefix first.  map "reference" (modOneSymbol's bin placement)
+    or "rx" (the placement the receivers undo); norm "peak" (row / max|row|)
+    or "scale" (row * scale).  return_peak: also the (...,) float32 peaks
+    max_n |x[n]| before scaling."""
+    import torch
+    if map not in TX_MAPS or norm not in TX_NORMS:
+        raise OfdmError(f"map must be one of {sorted(TX_MAPS)} and norm one of {sorted(TX_NORMS)}")
+    if ldx is None:
+        ldx = X.shape[-1]
+    if X.shape[-1] != ldx:
+        raise OfdmError(f"X's last dimension is {X.shape[-1]}, not ldx={ldx}")
+    lead = tuple(X.shape[:-1])
+    nrows = X.numel() // ldx if ldx else 0
+    if out is None:
+        out = c64(lead + (C + cp,), X.device)
+    peak = torch.empty(lead, dtype=torch.float32, device=X.device) if return_peak else None
+    _check(lib().ofdm_tx_modulate(_dptr(X, "X") if nrows else None, ldx, nrows, C, cp, TX_MAPS[map], TX_NORMS[norm],
+                                  scale, _dptr(out, "out") if nrows else None, _opt_ptr(peak, "peak") if nrows else None,
+                                  _stream(stream)), "ofdm_tx_modulate")
+    return (out, peak) if return_peak else out
 
 
 class Pipeline:

@@ -470,6 +470,62 @@ int ofdm_zf_apply_ex(const ofdm_cf32 *d_Wt, const ofdm_cf32 *d_X, long long ldx,
 int ofdm_zf_detect_ex(const ofdm_cf32 *d_Wt, const ofdm_cf32 *d_Y, long long ldy, int users, int rows, int K,
                       long long nsym, ofdm_cf32 *d_X, long long ldx, ofdm_stream_t stream);
 
+/* ------------------------------------------------------ OFDM modulator --- */
+
+/* The reference's transmit helpers in one pass per row (no version step:
+ * OFDM_LSMRC_VERSION stays 2): modOneSymbol / modRefSymbol
+ * (cpuLS.hpp:466-529) = bin placement with ifftShiftOneRow (119-132), the
+ * backward transform (ifftOneRow, 152-162), the per-row peak normalisation
+ * (clange_ 'M' then cblas_csscal, 521-523) and addPrefix (391-398).
+ *
+ * Input:  d_X[row*ldx + k], k < K = C - 1, ldx >= K; the pad is never read.
+ *         ldx = K is the layout of modOneSymbol's X and of ofdm_zf_apply's
+ *         output, ldx = 1024 takes ofdm_zf_apply_ex's padded rows (K = 1023).
+ * Output: d_iq[row*(C+cp_len) + n]: the prefix (the row's last cp_len
+ *         samples) first, then its C samples (addPrefix, cpuLS.hpp:394-395) --
+ *         the ring's `symbol` layout, so nrows = F*S*R rows written in order
+ *         are directly an input of ofdm_frame_demod.
+ *         d_peak (NULL = not wanted): d_peak[row] = max_n |x[n]| of the
+ *         transformed row BEFORE scaling, |x| = sqrt(re^2 + im^2) -- what
+ *         clange_ returns; with OFDM_TX_NORM_PEAK the gain 1/d_peak[row] a
+ *         caller needs to undo.
+ * Bin placement (which bin of the transform carries X[k]):
+ *   OFDM_TX_MAP_REFERENCE  modOneSymbol's, literally (cpuLS.hpp:511-513):
+ *         d[0] = 0, d[k+1] = X[k], then ifftShiftOneRow's three memmoves with
+ *         h = C/2 (integer): bin[i] = d[i+h] (i < h), bin[i] = d[i-h]
+ *         (h <= i < 2h) and, for odd C, bin[C-1] = d[C-1] left in place.  For
+ *         even C, X[k] sits at bin (k + 1 + C/2) mod C: bin C/2 is empty and
+ *         bin 0 (DC) carries X[C/2 - 1], which the receivers drop
+ *         (cpuLS.hpp:290-292) -- the reference's transmitter and receiver do
+ *         not agree; reproduced, not repaired.
+ *   OFDM_TX_MAP_RX  the placement the receivers undo: row position k at bin
+ *         out_src(k) + 1, out_src the inverse of shiftOneRow's output rotation
+ *         (cpuLS.hpp:135-149, the three memmoves for any K, even K included);
+ *         bin 0 empty.  A frame whose symbol 0 is the RAW pilot file order
+ *         (before matrix_readX's rotation, cpuLS.hpp:105-112) and whose
+ *         symbols 1..S-1 are data rows comes back from ofdm_frame_demod(X =
+ *         ofdm_pilot_rotate(raw)) as those data rows.
+ * Transform: backward, unnormalised, e^(+2 pi i n k / C) (FFTW_BACKWARD,
+ *   cpuLS.hpp:157).
+ * Scaling:
+ *   OFDM_TX_NORM_PEAK   row * (1 / max_n |x[n]|) (maxval = 1 / clange_, then
+ *         csscal, cpuLS.hpp:521-523; `scale` ignored).  An all-zero row is
+ *         stored as zeros with d_peak = 0; the reference would store NaN
+ *         (0 * (1/0)).
+ *   OFDM_TX_NORM_SCALE  row * scale (scale = 1: the bare unnormalised IFFT).
+ *   Non-finite inputs propagate.
+ * Limits: 2 <= C <= 8192, 0 <= cp_len <= C, nrows >= 0; d_X, d_iq 8-B
+ * aligned.  Anything else is OFDM_E_ARG, before any device work; nrows == 0
+ * is OFDM_OK and launches nothing.  C = 1024 runs one wave per row (16-B
+ * stores when cp_len is even and d_iq is 16-B aligned), every other C one
+ * workgroup per row on the mixed-radix stages of ofdm_fft_rows. */
+#define OFDM_TX_MAP_REFERENCE 0
+#define OFDM_TX_MAP_RX 1
+#define OFDM_TX_NORM_PEAK 0
+#define OFDM_TX_NORM_SCALE 1
+int ofdm_tx_modulate(const ofdm_cf32 *d_X, long long ldx, long long nrows, int C, int cp_len, int map, int norm,
+                     float scale, ofdm_cf32 *d_iq, float *d_peak /* nullable */, ofdm_stream_t stream);
+
 /* --------------------------------------------------- synthetic frames --- */
 
 /* Deterministic synthetic frames for tests and benchmarks:
