@@ -552,6 +552,89 @@ int ofdm_frame_demod_ex(const ofdm_cf32 *d_iq, long long nframes, int S, int R, 
     return rc;
 }
 
+// sc16 IQ: the checks every sc16 frame entry makes after check_frame_args,
+// before any HIP call.
+static int check_sc16(const char *fn, float scale, int C) {
+    if (!(scale > 0.f && scale <= 3.402823466e38f))
+        return fail(OFDM_E_ARG, "%s: scale=%g, sc16 samples need a positive finite scale", fn, (double)scale);
+    if (C != 1024)
+        return fail(OFDM_E_UNSUPPORTED, "%s: C=%d (the sc16 receiver covers C = 1024; convert with "
+                                        "ofdm_iq_convert_sc16 and call the fp32 entry)", fn, C);
+    return OFDM_OK;
+}
+static inline const ofdm::sc16 *SC(const ofdm_sc16 *p) { return reinterpret_cast<const ofdm::sc16 *>(p); }
+static_assert(sizeof(ofdm_sc16) == 4 && sizeof(ofdm::sc16) == 4, "one dword per sc16 sample");
+
+int ofdm_iq_convert_sc16(const ofdm_sc16 *d_in, long long n, float scale, ofdm_cf32 *d_out, ofdm_stream_t stream) {
+    static const char *fn = "ofdm_iq_convert_sc16";
+    if (n < 0) return fail(OFDM_E_ARG, "%s: n < 0", fn);
+    if (!(scale > 0.f && scale <= 3.402823466e38f))
+        return fail(OFDM_E_ARG, "%s: scale=%g, sc16 samples need a positive finite scale", fn, (double)scale);
+    if (n == 0) return OFDM_OK;
+    if (!d_in || !d_out) return fail(OFDM_E_ARG, "%s: null pointer", fn);
+    if (!aligned(d_in, 16) || !aligned(d_out, 16)) return fail(OFDM_E_ARG, "%s: d_in and d_out must be 16-byte aligned", fn);
+    return hip_check(ofdm::launch_iq_sc16_to_cf32(SC(d_in), n, scale, F2(d_out), hs(stream)), fn);
+}
+
+int ofdm_frame_estimate_sc16(const ofdm_sc16 *d_iq, long long nframes, int S, int R, int C, int prefix, float scale,
+                             const ofdm_cf32 *d_X, void *d_ws, size_t ws_bytes_, ofdm_stream_t stream) {
+    static const char *fn = "ofdm_frame_estimate_sc16";
+    int rc = check_frame_args(d_iq, nframes, S, R, C, prefix, d_ws, fn);
+    if (rc) return rc;
+    if ((rc = check_sc16(fn, scale, C))) return rc;
+    if (!d_X) return fail(OFDM_E_ARG, "%s: null pilots", fn);
+    if (nframes == 0) return OFDM_OK;
+    Workspace w;
+    if ((rc = carve(d_ws, ws_bytes_, nframes, S, R, C, false, w))) return rc;
+    ws_forget(d_ws);
+    rc = hip_check(ofdm::launch_ls_td1024_sc16(SC(d_iq), nframes, S, R, prefix, scale, F2(d_X), w.Hc, w.P, 0,
+                                               hs(stream)),
+                   "ls_td1024_sc16");
+    if (rc == OFDM_OK) ws_record(d_ws, ws_bytes_, nframes, S, R, C, true, false);
+    return rc;
+}
+
+int ofdm_frame_combine_sc16(const ofdm_sc16 *d_iq, long long nframes, int S, int R, int C, int prefix, float scale,
+                            void *d_ws, size_t ws_bytes_, ofdm_cf32 *d_out, ofdm_stream_t stream) {
+    static const char *fn = "ofdm_frame_combine_sc16";
+    if (int st = take_status(fn)) return st;
+    int rc = check_frame_args(d_iq, nframes, S, R, C, prefix, d_out, fn);
+    if (rc) return rc;
+    if ((rc = check_sc16(fn, scale, C))) return rc;
+    if (nframes == 0) return OFDM_OK;
+    WsTag tag;
+    if ((rc = ws_check(d_ws, ws_bytes_, nframes, S, R, C, true, fn, &tag))) return rc;
+    if (!tag.lane_order)
+        return fail(OFDM_E_ARG, "%s: the workspace holds a frequency-domain estimate (use ofdm_frame_combine_freq)", fn);
+    Workspace w;
+    if ((rc = carve(d_ws, ws_bytes_, nframes, S, R, C, false, w))) return rc;
+    return hip_check(ofdm::launch_mrc_td1024_sc16(SC(d_iq), nframes, S, R, prefix, scale, w.Hc, w.P, F2(d_out), 0,
+                                                  hs(stream)),
+                     "mrc_td1024_sc16");
+}
+
+int ofdm_frame_demod_sc16(const ofdm_sc16 *d_iq, long long nframes, int S, int R, int C, int prefix, float scale,
+                          const ofdm_cf32 *d_X, void *d_ws, size_t ws_bytes_, ofdm_cf32 *d_out, ofdm_stream_t stream) {
+    static const char *fn = "ofdm_frame_demod_sc16";
+    if (int st = take_status(fn)) return st;
+    int rc = check_frame_args(d_iq, nframes, S, R, C, prefix, d_out, fn);
+    if (rc) return rc;
+    if ((rc = check_sc16(fn, scale, C))) return rc;
+    if (!d_X) return fail(OFDM_E_ARG, "%s: null pilots", fn);
+    if (nframes == 0) return OFDM_OK;
+    Workspace w;
+    if ((rc = carve(d_ws, ws_bytes_, nframes, S, R, C, false, w))) return rc;
+    hipStream_t s = hs(stream);
+    ws_forget(d_ws);
+    rc = hip_check(ofdm::launch_ls_td1024_sc16(SC(d_iq), nframes, S, R, prefix, scale, F2(d_X), w.Hc, w.P, 0, s),
+                   "ls_td1024_sc16");
+    if (rc) return rc;
+    // the estimate is in the workspace once the LS launch is enqueued
+    ws_record(d_ws, ws_bytes_, nframes, S, R, C, true, false);
+    return hip_check(ofdm::launch_mrc_td1024_sc16(SC(d_iq), nframes, S, R, prefix, scale, w.Hc, w.P, F2(d_out), 0, s),
+                     "mrc_td1024_sc16");
+}
+
 int ofdm_frame_estimate_freq(const ofdm_cf32 *d_Y, long long nframes, int S, int R, int C,
                              const ofdm_cf32 *d_X, void *d_ws, size_t ws_bytes_, ofdm_stream_t stream) {
     int rc = check_frame_args(d_Y, nframes, S, R, C, 0, d_ws, "ofdm_frame_estimate_freq");

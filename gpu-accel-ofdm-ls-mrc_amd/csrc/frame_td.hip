@@ -47,13 +47,15 @@ namespace td1024 {
 // antennas -- the frame's rows are transformed side by side instead of four
 // after one another).
 // ---------------------------------------------------------------------------
+// IQ = sc16: the raw integers are transformed and the estimate multiplied by
+// `scale` (ignored for float2), so Hc and P are in the units of x = i16 * scale.
 constexpr int LS_WAVES = 4;
 
-template <int NW>
-__global__ void __launch_bounds__(64 * NW) k_ls_td1024(const float2 *__restrict__ iq, int S, int R,
+template <int NW, class IQ>
+__global__ void __launch_bounds__(64 * NW) k_ls_td1024(const IQ *__restrict__ iq, int S, int R,
                                                        int prefix, const float2 *__restrict__ X,
                                                        float2 *__restrict__ Hc, float *__restrict__ P,
-                                                       int partial) {
+                                                       int partial, float scale) {
     extern __shared__ __attribute__((aligned(16))) float2 lds[];
     float2 *tw = lds;
     const int w = threadIdx.x >> 6;
@@ -64,7 +66,7 @@ __global__ void __launch_bounds__(64 * NW) k_ls_td1024(const float2 *__restrict_
 
     const long long f = blockIdx.x;
     const int Cp = C + prefix;
-    const float2 *pilot = iq + f * (long long)S * R * Cp + prefix;
+    const IQ *pilot = iq + f * (long long)S * R * Cp + prefix;
     float4 *Hf = reinterpret_cast<float4 *>(Hc + f * (long long)R * C);
     const int b0 = lane_bin0(t);
     float2 xp[16];  // rotated pilots of this lane's subcarriers
@@ -78,11 +80,18 @@ __global__ void __launch_bounds__(64 * NW) k_ls_td1024(const float2 *__restrict_
     for (int k = 0; k < 16; ++k) p[k] = 0.f;
     for (int r = w; r < R; r += NW) {
         float2 a[16], x[16];
-        row_load(pilot + (long long)r * Cp, t, a);
+        if constexpr (is_sc16<IQ>) {
+            unsigned raw[16];
+            row_load(pilot + (long long)r * Cp, t, raw);
+            widen_row(raw, a);
+        } else {
+            row_load(pilot + (long long)r * Cp, t, a);
+        }
         row_fft(a, t, T, tw, x);
 #pragma unroll
         for (int k = 0; k < 16; ++k) {
             float2 h = ls_conj(x[k], xp[k]);
+            if constexpr (is_sc16<IQ>) h = float2{h.x * scale, h.y * scale};
             if (b0 + 16 * k == 0) h = float2{0.f, 0.f};
             x[k] = h;
             p[k] = p[k] + (h.x * h.x) + (h.y * h.y);
@@ -146,20 +155,34 @@ __device__ __forceinline__ void mac(float2 &acc, float2 x, float vx, float vy) {
 // (row, this wave's 1 KiB), in SGPRs; the lane's offset is formed here -- so
 // that no per-thread 64-bit pointer stays live across the loop.
 typedef int v4i_t __attribute__((ext_vector_type(4)));
-template <bool PREF>
-__device__ __forceinline__ void hlds_row_pf(const float2 *next, __amdgpu_buffer_rsrc_t hc, int hoff, int t,
-                                            float2 (&a)[16],
+template <bool PREF, class IQ>
+__device__ __forceinline__ void hlds_row_pf(const IQ *next, __amdgpu_buffer_rsrc_t hc, int hoff, int t,
+                                            row_reg_t<IQ> (&a)[16],
                                             float2 *T, const float2 *tw1, const float2 *tw2,
                                             const float4 *lo, const float4 *hi, float4 *mine,
                                             float2 (&acc)[16]) {
     using namespace hlds;
     float2 x[16];
-    fft_a(a, t, T, tw1);
+    if constexpr (is_sc16<IQ>) {
+        // widened only now: converting behind the load would put the wait for
+        // the prefetched row in front of the previous row's second FFT half
+        float2 af[16];
+        widen_row(a, af);
+        fft_a(af, t, T, tw1);
+    } else {
+        fft_a(a, t, T, tw1);
+    }
     // a row is 512 float4: each of the 512 threads moves 16 B
     const float4 hreg = __builtin_bit_cast(float4, (v4i_t)__builtin_amdgcn_raw_buffer_load_b128(hc, t * 16, hoff, 0));
     __builtin_amdgcn_sched_barrier(0);
     if (PREF) row_load<true>(next, t, a);
     fft_b(t, T, tw2, x);
+    // sc16: the second FFT half stays in front of the exchange, as the fp32
+    // loop has it (left free, the scheduler moves it between the two barriers
+    // and the allocator then spills six accumulators across the loop, whose
+    // reloads wait for the prefetched row: 128 VGPRs + 24 B of scratch
+    // against 112 and none)
+    if constexpr (is_sc16<IQ>) __builtin_amdgcn_sched_barrier(0);
     lds_barrier();  // every wave is done with the previous Hc row
     *mine = hreg;
     lds_barrier();
@@ -176,12 +199,15 @@ __device__ __forceinline__ void hlds_row_pf(const float2 *next, __amdgpu_buffer_
 // as the first FFT half has written a[] to the transpose image (in flight
 // during the second half, the Hc exchange and the MAC; no extra registers).
 // Otherwise (a workgroup straddling a frame boundary) each wave loads its
-// own Hc row from L2.
+// own Hc row from L2.  sc16 rows (IQ = sc16) go through the transform and
+// the MAC as raw integers (|sums| <= 2^15 * 1024 * R: exact headroom in f32);
+// the scale is applied once per output, in the epilogue.
 // R0: row 0 is already in this wave's transpose image, DMA'd there at the
 // workgroup's start (row0_dma) and landed (vmcnt drained, barrier passed).
-template <bool R0>
-__device__ __forceinline__ void row0(const float2 *sym, int t, const float2 *T, float2 (&a)[16]) {
+template <bool R0, class IQ>
+__device__ __forceinline__ void row0(const IQ *sym, int t, const float2 *T, row_reg_t<IQ> (&a)[16]) {
     if constexpr (R0) {
+        static_assert(!is_sc16<IQ>, "sc16 rows are only 4-byte aligned: no 16-B row-0 DMA");
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's DMA (the compiler does not count asm loads)
 #pragma unroll
         for (int m = 0; m < 16; ++m) a[m] = T[t + 64 * m];
@@ -200,15 +226,15 @@ __device__ __forceinline__ void row0_dma(const float2 *sym, int t, float2 *T) {
     for (int j = 0; j < 8; ++j) dma16(src + j * 1024, dst + j * 1024);
 }
 
-template <bool SHARED, bool R0 = false>
-__device__ __forceinline__ void hlds_rows(const float2 *sym, int Cp, int R, const float4 *Hf, int t,
+template <bool SHARED, bool R0 = false, class IQ>
+__device__ __forceinline__ void hlds_rows(const IQ *sym, int Cp, int R, const float4 *Hf, int t,
                                           float2 *T, const float2 *tw1, const float2 *tw2,
                                           float2 *T0, float4 *hfree, float2 (&acc)[16]) {
     using namespace hlds;
 #pragma unroll
     for (int k = 0; k < 16; ++k) acc[k] = float2{0.f, 0.f};
     if constexpr (SHARED) {
-        float2 a[16];
+        row_reg_t<IQ> a[16];
         const int tl = lane_here();  // the caller's t need not stay live up to here
         row0<R0>(sym, tl, T, a);
         const float4 *lo = hfree + tl;
@@ -227,10 +253,18 @@ __device__ __forceinline__ void hlds_rows(const float2 *sym, int Cp, int R, cons
     } else {
         for (int r = 0; r < R; ++r) {
             float2 a[16], x[16], h[16];
-            if (r == 0)
+            if constexpr (is_sc16<IQ>) {
+                unsigned raw[16];
+                if (r == 0)
+                    row0<R0>(sym, t, T, raw);
+                else
+                    row_load<true>(sym + (long long)r * Cp, t, raw);
+                widen_row(raw, a);
+            } else if (r == 0) {
                 row0<R0>(sym, t, T, a);
-            else
+            } else {
                 row_load<true>(sym + (long long)r * Cp, t, a);
+            }
             fft_a(a, t, T, tw1);
             fft_b(t, T, tw2, x);
             __builtin_amdgcn_sched_barrier(0);
@@ -246,8 +280,12 @@ __device__ __forceinline__ void hlds_rows(const float2 *sym, int Cp, int R, cons
 // still hold other waves' Hc words, so index it as [16][TP]) at their final
 // positions, then store them as 16 contiguous 512-B nontemporal wave stores
 // instead of 4 scattered 128-B runs per instruction.
+// SCALED (the sc16 receiver, whose acc is in raw integer units): scale folded
+// into the reciprocal (mode 0) or applied to the numerator (mode 1).
+template <bool SCALED = false>
 __device__ __forceinline__ void hlds_epilogue(const float2 (&acc)[16], const float *P, long long f, long long q,
-                                              int t, float2 *T, float2 *__restrict__ out, int mode) {
+                                              int t, float2 *T, float2 *__restrict__ out, int mode,
+                                              float scale = 1.f) {
     const int b0 = lane_bin0(t);
     float2 *o = out + q * K;
     const float *Pf = P + f * C + b0;
@@ -268,9 +306,12 @@ __device__ __forceinline__ void hlds_epilogue(const float2 (&acc)[16], const flo
             // acc * (1 / P): one reciprocal (v_rcp_f32, 1 ulp) and two
             // products instead of two IEEE divisions (10 instructions each);
             // within 2 ulp of the reference's division (cpuLS.hpp:364-368)
-            const float rp = __builtin_amdgcn_rcpf(pv[k]);
+            float rp = __builtin_amdgcn_rcpf(pv[k]);
+            if constexpr (SCALED) rp = rp * scale;
             v = float2{acc[k].x * rp, acc[k].y * rp};
             j = out_pos(b > 0 ? b - 1 : 0, K);
+        } else if constexpr (SCALED) {
+            v = float2{acc[k].x * scale, acc[k].y * scale};
         }
         if (b > 0) T[(j >> 6) * hlds::TP + (j & 63)] = v;
     }
@@ -291,11 +332,12 @@ __device__ __forceinline__ void hlds_epilogue(const float2 (&acc)[16], const flo
 // (blocks b and b+8 share an XCD under round-robin dispatch, so a frame's
 // workgroups share its Hc rows in one L2; speed only, never correctness).
 // mode 0: out[q][out_pos(j)] = acc / P;  mode 1: out[q][j] = acc (numerator).
-template <bool R0>
+// IQ = sc16: `scale` (ignored for float2) turns the raw integers into samples.
+template <bool R0, class IQ>
 __global__ void __attribute__((amdgpu_flat_work_group_size(512, 512), amdgpu_waves_per_eu(4, 4)))
-k_mrc_td1024_hlds(const float2 *__restrict__ iq, int S, int R, int prefix, const float2 *__restrict__ Hc,
+k_mrc_td1024_hlds(const IQ *__restrict__ iq, int S, int R, int prefix, const float2 *__restrict__ Hc,
                   const float *__restrict__ P, float2 *__restrict__ out, long long nq, long long nblocks,
-                  long long per_xcd, int mode) {
+                  long long per_xcd, int mode, float scale) {
     using namespace hlds;
     constexpr int HW = WAVES;
     extern __shared__ __attribute__((aligned(16))) float2 lds[];
@@ -321,7 +363,7 @@ k_mrc_td1024_hlds(const float2 *__restrict__ iq, int S, int R, int prefix, const
     const long long fl = ((lb * HW + HW - 1 < nq ? lb * HW + HW - 1 : nq - 1)) / nsym;
     const int s = 1 + (int)(q % nsym);
     const int Cp = C + prefix;
-    const float2 *sym = iq + (f * S + s) * (long long)R * Cp + prefix;
+    const IQ *sym = iq + (f * S + s) * (long long)R * Cp + prefix;
     if constexpr (R0) row0_dma(sym, t, T);
     fill(tw1, tw2);
     __syncthreads();
@@ -334,7 +376,10 @@ k_mrc_td1024_hlds(const float2 *__restrict__ iq, int S, int R, int prefix, const
         hlds_rows<false, R0>(sym, Cp, R, reinterpret_cast<const float4 *>(Hc + f * (long long)R * C), t, T,
                                 tw1, tw2, T0, hfree, acc);
     if (!store) return;
-    hlds_epilogue(acc, P, f, q, lane_here(), T, out, mode);
+    if constexpr (is_sc16<IQ>)
+        hlds_epilogue<true>(acc, P, f, q, lane_here(), T, out, mode, scale);
+    else
+        hlds_epilogue(acc, P, f, q, lane_here(), T, out, mode);
 }
 
 
@@ -587,34 +632,36 @@ k_demod_td1024(const float2 *__restrict__ iq, int S, int R, int prefix, const fl
 
 }  // namespace td1024
 
-hipError_t launch_ls_td1024(const float2 *iq, long long nframes, int S, int R, int prefix,
-                            const float2 *X, float2 *Hc, float *P, int partial, hipStream_t s) {
+namespace {
+template <class IQ>
+hipError_t ls_td1024(const IQ *iq, long long nframes, int S, int R, int prefix, float scale,
+                     const float2 *X, float2 *Hc, float *P, int partial, hipStream_t s) {
     using namespace td1024;
     if (nframes <= 0) return hipSuccess;
     if (nframes > 0x7fffffffll) return hipErrorInvalidValue;
     // 4-wave workgroups unless they leave the GPU under-filled: fewer than
     // 2 waves per SIMD (2048 waves) with rows left to spread
     int nw = (nframes * LS_WAVES < 2048 && R > LS_WAVES) ? 16 : LS_WAVES;
-    auto k16 = k_ls_td1024<16>;
-    auto k4 = k_ls_td1024<LS_WAVES>;
+    auto k16 = k_ls_td1024<16, IQ>;
+    auto k4 = k_ls_td1024<LS_WAVES, IQ>;
     auto k8 = k16;  // 8-wave workgroups: A/B build only
     if (nw == 16 || nw == 8) {
         auto kern = nw == 16 ? k16 : k8;
         const size_t lds = (TWBUF + nw * TBUF) * sizeof(float2);
         if (hipError_t e = opt_in_lds(reinterpret_cast<const void *>(kern), (int)lds); e != hipSuccess) return e;
         hipLaunchKernelGGL(kern, dim3((unsigned)nframes), dim3(64 * nw), lds, s, iq, S, R, prefix, X, Hc, P,
-                           partial);
+                           partial, scale);
         return hipGetLastError();
     }
     const size_t lds = (TWBUF + LS_WAVES * TBUF) * sizeof(float2);
     hipLaunchKernelGGL(k4, dim3((unsigned)nframes), dim3(64 * LS_WAVES), lds, s, iq, S, R, prefix, X, Hc, P,
-                       partial);
+                       partial, scale);
     return hipGetLastError();
 }
 
-hipError_t launch_mrc_td1024(const float2 *iq, long long nframes, int S, int R, int prefix,
-                             const float2 *Hc, const float *P, float2 *out, int mode,
-                             hipStream_t s) {
+template <class IQ>
+hipError_t mrc_td1024(const IQ *iq, long long nframes, int S, int R, int prefix, float scale,
+                      const float2 *Hc, const float *P, float2 *out, int mode, hipStream_t s) {
     using namespace td1024;
     const long long nq = nframes * (S - 1);
     if (nq <= 0) return hipSuccess;
@@ -626,10 +673,31 @@ hipError_t launch_mrc_td1024(const float2 *iq, long long nframes, int S, int R, 
     // R=64 x 400 3.961 -> 3.922; profiles/r3/r3p_row0_dma_ab.jsonl).  The
     // one-launch kernel takes it too since round 6, once its receivers ran
     // without scratch (profiles/r6/r6m2_*).
-    auto kern = k_mrc_td1024_hlds<true>;
+    // sc16 rows are only 4-byte aligned (any cp_len): their row 0 comes by
+    // naturally aligned dword loads like every other row, not by 16-B DMA.
+    auto kern = k_mrc_td1024_hlds<!is_sc16<IQ>, IQ>;
     hipLaunchKernelGGL(kern, dim3((unsigned)(pxcd * 8)), dim3(64 * hlds::WAVES), hlds::LDS_BYTES, s, iq, S, R,
-                       prefix, Hc, P, out, nq, nb, pxcd, mode);
+                       prefix, Hc, P, out, nq, nb, pxcd, mode, scale);
     return hipGetLastError();
+}
+}  // namespace
+
+hipError_t launch_ls_td1024(const float2 *iq, long long nframes, int S, int R, int prefix,
+                            const float2 *X, float2 *Hc, float *P, int partial, hipStream_t s) {
+    return ls_td1024(iq, nframes, S, R, prefix, 1.f, X, Hc, P, partial, s);
+}
+hipError_t launch_ls_td1024_sc16(const sc16 *iq, long long nframes, int S, int R, int prefix, float scale,
+                                 const float2 *X, float2 *Hc, float *P, int partial, hipStream_t s) {
+    return ls_td1024(iq, nframes, S, R, prefix, scale, X, Hc, P, partial, s);
+}
+hipError_t launch_mrc_td1024(const float2 *iq, long long nframes, int S, int R, int prefix,
+                             const float2 *Hc, const float *P, float2 *out, int mode,
+                             hipStream_t s) {
+    return mrc_td1024(iq, nframes, S, R, prefix, 1.f, Hc, P, out, mode, s);
+}
+hipError_t launch_mrc_td1024_sc16(const sc16 *iq, long long nframes, int S, int R, int prefix, float scale,
+                                  const float2 *Hc, const float *P, float2 *out, int mode, hipStream_t s) {
+    return mrc_td1024(iq, nframes, S, R, prefix, scale, Hc, P, out, mode, s);
 }
 
 // One-launch LS + MRC (ofdm_frame_demod, mode 0).  flags: nframes 64-bit

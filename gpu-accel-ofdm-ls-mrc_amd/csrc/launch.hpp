@@ -134,6 +134,23 @@ hipError_t launch_demod_td1024(const float2 *iq, long long nframes, int S, int R
                                unsigned long long *flags, unsigned long long epoch, long long spin_ticks,
                                hipStream_t s);
 
+// One sc16 sample as the radio puts it on the wire (ofdm_sc16: int16 re in
+// the low half of the little-endian dword, int16 im in the high half).
+struct sc16 {
+    unsigned v;
+};
+// The two-launch C = 1024 receiver on sc16 frames (the same kernels,
+// instantiated on the sample type): the fp32 launchers' contracts applied to
+// x = (float)i16 * scale.  Hc and P come out in true units, so a workspace
+// serves either format's MRC.  Rows need 4-byte alignment only.
+hipError_t launch_ls_td1024_sc16(const sc16 *iq, long long nframes, int S, int R, int prefix, float scale,
+                                 const float2 *X, float2 *Hc, float *P, int partial, hipStream_t s);
+hipError_t launch_mrc_td1024_sc16(const sc16 *iq, long long nframes, int S, int R, int prefix, float scale,
+                                  const float2 *Hc, const float *P, float2 *out, int mode, hipStream_t s);
+// out[i] = {float(re) * scale, float(im) * scale}, i < n (iq_sc16.hip); in
+// and out 16-B aligned.
+hipError_t launch_iq_sc16_to_cf32(const sc16 *in, long long n, float scale, float2 *out, hipStream_t s);
+
 // Stage-wise operations of the reference's per-stage gpuLS methods (stages.hip).
 // fused time-domain receiver, C = 2048 (frame_td2048.hip); same contracts
 hipError_t launch_ls_td2048(const float2 *iq, long long nframes, int S, int R, int prefix,

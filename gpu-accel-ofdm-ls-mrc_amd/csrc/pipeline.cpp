@@ -27,7 +27,8 @@
 
 struct ofdm_pipeline {
     struct Slot {
-        ofdm_cf32 *iq = nullptr;
+        void *iq = nullptr;          // chunk frames of ofdm_cf32, or of ofdm_sc16 (sc16 pipelines)
+        ofdm_cf32 *f32 = nullptr;    // sc16 pipelines at C != 1024: the converted chunk
         ofdm_cf32 *out = nullptr;
         void *ws = nullptr;
         hipEvent_t in_done = nullptr, comp_done = nullptr, out_done = nullptr;
@@ -35,6 +36,8 @@ struct ofdm_pipeline {
         bool acquired = false;   // acquire() called, submit() pending
     };
     int S = 0, R = 0, C = 0, cp = 0, K = 0, device = 0;
+    bool sc16 = false;  // the slots hold ofdm_sc16 samples, x = i16 * scale
+    float scale = 1.f;
     long long chunk = 0;
     size_t ws_bytes = 0, frame_in = 0, frame_out = 0;  // elements
     ofdm_cf32 *X = nullptr;
@@ -84,6 +87,7 @@ void release(ofdm_pipeline *p) {
     DeviceGuard dg(p->device);
     for (auto &s : p->slots) {
         if (s.iq) (void)hipFree(s.iq);
+        if (s.f32) (void)hipFree(s.f32);
         if (s.out) (void)hipFree(s.out);
         if (s.ws) {
             (void)ofdm_workspace_release(s.ws);  // its registry entry must not outlive the memory
@@ -100,17 +104,15 @@ void release(ofdm_pipeline *p) {
     delete p;
 }
 
-}  // namespace
-
-extern "C" {
-
-int ofdm_pipeline_create(int S, int R, int C, int cp_len, const ofdm_cf32 *X, int chunk_frames,
-                         int depth, ofdm_pipeline **out) {
-    static const char *fn = "ofdm_pipeline_create";
+// ofdm_pipeline_create / _create_sc16
+int create(const char *fn, int S, int R, int C, int cp_len, bool sc16, float scale, const ofdm_cf32 *X,
+           int chunk_frames, int depth, ofdm_pipeline **out) {
     if (!out || !X) return err(OFDM_E_ARG, fn, "null pointer");
     *out = nullptr;
     if (chunk_frames < 1 || depth < 1 || depth > 64)
         return err(OFDM_E_ARG, fn, "chunk_frames >= 1 and 1 <= depth <= 64 required");
+    if (sc16 && !(scale > 0.f && scale <= 3.402823466e38f))
+        return err(OFDM_E_ARG, fn, "sc16 samples need a positive finite scale");
     const size_t ws = ofdm_frame_workspace_bytes(chunk_frames, S, R, C);
     if (ws == 0) return err(OFDM_E_UNSUPPORTED, fn, "bad frame geometry (S >= 2, R >= 1, 2 <= C <= 8192)");
     if (cp_len < 0 || cp_len > C) return err(OFDM_E_ARG, fn, "cp_len out of [0, C]");
@@ -118,6 +120,8 @@ int ofdm_pipeline_create(int S, int R, int C, int cp_len, const ofdm_cf32 *X, in
     if (!p) return err(OFDM_E_ARG, fn, "out of host memory");
     p->S = S; p->R = R; p->C = C; p->cp = cp_len; p->K = C - 1;
     p->chunk = chunk_frames;
+    p->sc16 = sc16;
+    p->scale = scale;
     p->ws_bytes = ws;
     p->frame_in = (size_t)S * R * (C + cp_len);
     p->frame_out = (size_t)(S - 1) * (C - 1);
@@ -135,7 +139,10 @@ int ofdm_pipeline_create(int S, int R, int C, int cp_len, const ofdm_cf32 *X, in
     CR(hipMemcpy(p->X, X, (size_t)(C - 1) * sizeof(ofdm_cf32), hipMemcpyDefault), "copy X");
     p->slots.resize(depth);
     for (auto &s : p->slots) {
-        CR(hipMalloc(&s.iq, p->frame_in * chunk_frames * sizeof(ofdm_cf32)), "hipMalloc(iq slot)");
+        CR(hipMalloc(&s.iq, p->frame_in * chunk_frames * (sc16 ? sizeof(ofdm_sc16) : sizeof(ofdm_cf32))),
+           "hipMalloc(iq slot)");
+        if (sc16 && C != 1024)  // no sc16 receiver at this C: converted, then the fp32 one
+            CR(hipMalloc(&s.f32, p->frame_in * chunk_frames * sizeof(ofdm_cf32)), "hipMalloc(fp32 slot)");
         CR(hipMalloc(&s.out, p->frame_out * chunk_frames * sizeof(ofdm_cf32)), "hipMalloc(out slot)");
         CR(hipMalloc(&s.ws, ws), "hipMalloc(workspace)");
         CR(hipEventCreateWithFlags(&s.in_done, hipEventDisableTiming), "hipEventCreate");
@@ -147,16 +154,12 @@ int ofdm_pipeline_create(int S, int R, int C, int cp_len, const ofdm_cf32 *X, in
     return OFDM_OK;
 }
 
-int ofdm_pipeline_destroy(ofdm_pipeline *p) {
-    if (!p) return OFDM_OK;
-    const int rc = ofdm_pipeline_sync(p);
-    release(p);
-    return rc;
-}
-
-int ofdm_pipeline_acquire(ofdm_pipeline *p, ofdm_cf32 **d_iq, ofdm_stream_t *copy_stream) {
-    static const char *fn = "ofdm_pipeline_acquire";
+// the acquire of either format (fmt_sc16: the caller's)
+int acquire(const char *fn, ofdm_pipeline *p, bool fmt_sc16, void **d_iq, ofdm_stream_t *copy_stream) {
     if (!p || !d_iq) return err(OFDM_E_ARG, fn, "null pointer");
+    if (p->sc16 != fmt_sc16)
+        return err(OFDM_E_ARG, fn, p->sc16 ? "the pipeline holds sc16 samples (use the _sc16 entry)"
+                                           : "the pipeline holds fp32 samples (use the entry without _sc16)");
     auto &s = p->slots[p->next];
     if (s.acquired) return err(OFDM_E_ARG, fn, "slot already acquired: submit it first");
     DeviceGuard dg(p->device);
@@ -167,6 +170,57 @@ int ofdm_pipeline_acquire(ofdm_pipeline *p, ofdm_cf32 **d_iq, ofdm_stream_t *cop
     *d_iq = s.iq;
     if (copy_stream) *copy_stream = reinterpret_cast<ofdm_stream_t>(p->s_in);
     return OFDM_OK;
+}
+
+// acquire + copy + submit over nframes host frames of `esize`-byte samples
+int demod_all(const char *fn, ofdm_pipeline *p, bool fmt_sc16, const void *iq, size_t esize, long long nframes,
+              ofdm_cf32 *out) {
+    if (!p) return err(OFDM_E_ARG, fn, "null pipeline");
+    if (nframes < 0 || (nframes > 0 && (!iq || !out))) return err(OFDM_E_ARG, fn, "bad arguments");
+    if (p->sc16 != fmt_sc16)
+        return err(OFDM_E_ARG, fn, p->sc16 ? "the pipeline holds sc16 samples (use the _sc16 entry)"
+                                           : "the pipeline holds fp32 samples (use the entry without _sc16)");
+    for (long long f0 = 0; f0 < nframes; f0 += p->chunk) {
+        const long long n = nframes - f0 < p->chunk ? nframes - f0 : p->chunk;
+        void *d = nullptr;
+        ofdm_stream_t cs = nullptr;
+        int rc = acquire(fn, p, fmt_sc16, &d, &cs);
+        if (rc) return rc;
+        PL_TRY(hipMemcpyAsync(d, static_cast<const char *>(iq) + (size_t)f0 * p->frame_in * esize,
+                              (size_t)n * p->frame_in * esize, hipMemcpyDefault, reinterpret_cast<hipStream_t>(cs)),
+               fn, "copy-in");
+        if ((rc = ofdm_pipeline_submit(p, n, out + (size_t)f0 * p->frame_out))) return rc;
+    }
+    return OFDM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ofdm_pipeline_create(int S, int R, int C, int cp_len, const ofdm_cf32 *X, int chunk_frames,
+                         int depth, ofdm_pipeline **out) {
+    return create("ofdm_pipeline_create", S, R, C, cp_len, false, 1.f, X, chunk_frames, depth, out);
+}
+
+int ofdm_pipeline_create_sc16(int S, int R, int C, int cp_len, float scale, const ofdm_cf32 *X, int chunk_frames,
+                              int depth, ofdm_pipeline **out) {
+    return create("ofdm_pipeline_create_sc16", S, R, C, cp_len, true, scale, X, chunk_frames, depth, out);
+}
+
+int ofdm_pipeline_destroy(ofdm_pipeline *p) {
+    if (!p) return OFDM_OK;
+    const int rc = ofdm_pipeline_sync(p);
+    release(p);
+    return rc;
+}
+
+int ofdm_pipeline_acquire(ofdm_pipeline *p, ofdm_cf32 **d_iq, ofdm_stream_t *copy_stream) {
+    return acquire("ofdm_pipeline_acquire", p, false, reinterpret_cast<void **>(d_iq), copy_stream);
+}
+
+int ofdm_pipeline_acquire_sc16(ofdm_pipeline *p, ofdm_sc16 **d_iq, ofdm_stream_t *copy_stream) {
+    return acquire("ofdm_pipeline_acquire_sc16", p, true, reinterpret_cast<void **>(d_iq), copy_stream);
 }
 
 int ofdm_pipeline_submit(ofdm_pipeline *p, long long nframes, ofdm_cf32 *out) {
@@ -204,8 +258,20 @@ int ofdm_pipeline_submit(ofdm_pipeline *p, long long nframes, ofdm_cf32 *out) {
     PL_TRY(hipStreamWaitEvent(p->s_comp, s.in_done, 0), fn, "hipStreamWaitEvent");
     if (s.used) PL_TRY(hipStreamWaitEvent(p->s_comp, s.out_done, 0), fn, "hipStreamWaitEvent");
     if (nframes > 0) {
-        const int rc = ofdm_frame_demod(s.iq, nframes, p->S, p->R, p->C, p->cp, p->X, s.ws,
-                                        p->ws_bytes, s.out, p->s_comp);
+        int rc;
+        if (!p->sc16) {
+            rc = ofdm_frame_demod(static_cast<const ofdm_cf32 *>(s.iq), nframes, p->S, p->R, p->C, p->cp, p->X, s.ws,
+                                  p->ws_bytes, s.out, p->s_comp);
+        } else if (!s.f32) {
+            rc = ofdm_frame_demod_sc16(static_cast<const ofdm_sc16 *>(s.iq), nframes, p->S, p->R, p->C, p->cp,
+                                       p->scale, p->X, s.ws, p->ws_bytes, s.out, p->s_comp);
+        } else {
+            rc = ofdm_iq_convert_sc16(static_cast<const ofdm_sc16 *>(s.iq), (long long)(nframes * p->frame_in),
+                                      p->scale, s.f32, p->s_comp);
+            if (rc == OFDM_OK)
+                rc = ofdm_frame_demod(s.f32, nframes, p->S, p->R, p->C, p->cp, p->X, s.ws, p->ws_bytes, s.out,
+                                      p->s_comp);
+        }
         if (rc) return rc;
     }
     PL_TRY(hipEventRecord(s.comp_done, p->s_comp), fn, "hipEventRecord");
@@ -224,21 +290,11 @@ int ofdm_pipeline_submit(ofdm_pipeline *p, long long nframes, ofdm_cf32 *out) {
 
 int ofdm_pipeline_demod(ofdm_pipeline *p, const ofdm_cf32 *iq, long long nframes,
                         ofdm_cf32 *out) {
-    static const char *fn = "ofdm_pipeline_demod";
-    if (!p) return err(OFDM_E_ARG, fn, "null pipeline");
-    if (nframes < 0 || (nframes > 0 && (!iq || !out))) return err(OFDM_E_ARG, fn, "bad arguments");
-    for (long long f0 = 0; f0 < nframes; f0 += p->chunk) {
-        const long long n = nframes - f0 < p->chunk ? nframes - f0 : p->chunk;
-        ofdm_cf32 *d = nullptr;
-        ofdm_stream_t cs = nullptr;
-        int rc = ofdm_pipeline_acquire(p, &d, &cs);
-        if (rc) return rc;
-        PL_TRY(hipMemcpyAsync(d, iq + (size_t)f0 * p->frame_in, (size_t)n * p->frame_in * sizeof(ofdm_cf32),
-                              hipMemcpyDefault, reinterpret_cast<hipStream_t>(cs)),
-               fn, "copy-in");
-        if ((rc = ofdm_pipeline_submit(p, n, out + (size_t)f0 * p->frame_out))) return rc;
-    }
-    return OFDM_OK;
+    return demod_all("ofdm_pipeline_demod", p, false, iq, sizeof(ofdm_cf32), nframes, out);
+}
+
+int ofdm_pipeline_demod_sc16(ofdm_pipeline *p, const ofdm_sc16 *iq, long long nframes, ofdm_cf32 *out) {
+    return demod_all("ofdm_pipeline_demod_sc16", p, true, iq, sizeof(ofdm_sc16), nframes, out);
 }
 
 int ofdm_pipeline_sync(ofdm_pipeline *p) {

@@ -101,6 +101,38 @@ __device__ __forceinline__ void row_load(const float2 *__restrict__ src, int t, 
     }
 }
 
+// sc16 rows (launch.hpp sc16: one dword per sample).  The same lane -> sample
+// map, a[m] = src[t + 64 m], as 16 coalesced 256-byte wave loads; the row
+// stays as its 16 raw dwords while it is in flight (a prefetched row holds 16
+// VGPRs, not 32) and is widened where it is consumed: one v_cvt_f32_i32 with
+// a sign-extending word select per component.
+template <class IQ>
+struct row_regs {
+    typedef float2 type;
+};
+template <>
+struct row_regs<sc16> {
+    typedef unsigned type;
+};
+template <class IQ>
+using row_reg_t = typename row_regs<IQ>::type;
+template <class IQ>
+constexpr bool is_sc16 = __is_same(IQ, sc16);
+
+template <bool NT = false>
+__device__ __forceinline__ void row_load(const sc16 *__restrict__ src, int t, unsigned (&a)[16]) {
+    const unsigned *p = reinterpret_cast<const unsigned *>(src) + t;
+#pragma unroll
+    for (int m = 0; m < 16; ++m) a[m] = NT ? __builtin_nontemporal_load(p + 64 * m) : p[64 * m];
+}
+__device__ __forceinline__ float2 widen(unsigned v) {
+    return float2{(float)(short)(v & 0xffffu), (float)((int)v >> 16)};
+}
+__device__ __forceinline__ void widen_row(const unsigned (&a)[16], float2 (&x)[16]) {
+#pragma unroll
+    for (int m = 0; m < 16; ++m) x[m] = widen(a[m]);
+}
+
 // v[k] = dpp(v[k]) * S + v[k] for 16 floats, one v_fmac_f32_dpp each (the
 // compiler would emit v_mov_dpp + fma + an s_nop per value).  The leading
 // s_nop 1 covers the "VALU writes VGPR -> DPP reads it" hazard (2 wait states)

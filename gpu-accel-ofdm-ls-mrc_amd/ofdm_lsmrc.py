@@ -71,6 +71,13 @@ _SIGS = {
     "ofdm_pipeline_submit": (_I, [_P, _LL, _P]),
     "ofdm_pipeline_demod": (_I, [_P, _P, _LL, _P]),
     "ofdm_pipeline_sync": (_I, [_P]),
+    "ofdm_iq_convert_sc16": (_I, [_P, _LL, _c.c_float, _P, _P]),
+    "ofdm_frame_demod_sc16": (_I, [_P, _LL, _I, _I, _I, _I, _c.c_float, _P, _P, _c.c_size_t, _P, _P]),
+    "ofdm_frame_estimate_sc16": (_I, [_P, _LL, _I, _I, _I, _I, _c.c_float, _P, _P, _c.c_size_t, _P]),
+    "ofdm_frame_combine_sc16": (_I, [_P, _LL, _I, _I, _I, _I, _c.c_float, _P, _c.c_size_t, _P, _P]),
+    "ofdm_pipeline_create_sc16": (_I, [_I, _I, _I, _I, _c.c_float, _P, _I, _I, _c.POINTER(_P)]),
+    "ofdm_pipeline_acquire_sc16": (_I, [_P, _c.POINTER(_P), _c.POINTER(_P)]),
+    "ofdm_pipeline_demod_sc16": (_I, [_P, _P, _LL, _P]),
     "ofdm_host_register": (_I, [_P, _c.c_size_t]),
     "ofdm_host_unregister": (_I, [_P]),
     "ofdm_pn_correlate": (_I, [_P, _I, _LL, _P, _I, _c.c_float, _P, _P, _P]),
@@ -371,6 +378,67 @@ def frame_combine(iq, prefix, ws, out, stream=None):
     return out
 
 
+SC16_SCALE = 2.0 ** -15  # the power-of-two scale; UHD's own convention is 1 / 32767
+
+
+def _sc16(t, name, ndim=None):
+    """The device pointer of a torch.int16 tensor of sc16 samples (..., 2)."""
+    import torch
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.int16 or t.shape[-1] != 2:
+        raise OfdmError(f"{name} must be a torch.int16 tensor whose last dimension is (re, im)")
+    if ndim is not None and t.dim() != ndim:
+        raise OfdmError(f"{name} must have {ndim} dimensions, not {t.dim()}")
+    return _dptr(t, name)
+
+
+def iq_convert_sc16(iq, scale=SC16_SCALE, out=None, stream=None):
+    """sc16 samples (..., 2) torch.int16 -> complex64 (...): x = i16 * scale per
+    component, one rounding (bit-exact).  The route to every fp32 entry for
+    the FFT lengths without an sc16 receiver."""
+    p = _sc16(iq, "iq")
+    n = iq.numel() // 2
+    if out is None:
+        out = c64(tuple(iq.shape[:-1]), iq.device)
+    _check(lib().ofdm_iq_convert_sc16(p if n else None, n, scale, _dptr(out, "out") if n else None, _stream(stream)),
+           "ofdm_iq_convert_sc16")
+    return out
+
+
+def frame_demod_sc16(iq, X, prefix=0, scale=SC16_SCALE, ws=None, out=None, stream=None):
+    """frame_demod on sc16 frames: iq (F, S, R, C+prefix, 2) torch.int16,
+    x = i16 * scale -> (F, S-1, K).  C = 1024 (else convert, then frame_demod)."""
+    p = _sc16(iq, "iq", 5)
+    F, S, R, Cp, _ = iq.shape
+    C = Cp - prefix
+    if ws is None:
+        ws = workspace(F, S, R, C, iq.device)
+    if out is None:
+        out = c64((F, S - 1, C - 1), iq.device)
+    _check(lib().ofdm_frame_demod_sc16(p, F, S, R, C, prefix, scale, _dptr(X), _dptr(ws), ws.numel(), _dptr(out),
+                                       _stream(stream)), "ofdm_frame_demod_sc16")
+    return out
+
+
+def frame_estimate_sc16(iq, X, prefix, ws, scale=SC16_SCALE, stream=None):
+    """LS stage of frame_demod_sc16; the estimate in ws is in the units of
+    x = i16 * scale and serves the fp32 consumers too."""
+    p = _sc16(iq, "iq", 5)
+    F, S, R, Cp, _ = iq.shape
+    _check(lib().ofdm_frame_estimate_sc16(p, F, S, R, Cp - prefix, prefix, scale, _dptr(X), _dptr(ws), ws.numel(),
+                                          _stream(stream)), "ofdm_frame_estimate_sc16")
+    return ws
+
+
+def frame_combine_sc16(iq, prefix, ws, out, scale=SC16_SCALE, stream=None):
+    """MRC stage of frame_demod_sc16 against the estimate in ws (made by
+    frame_estimate_sc16 or by the fp32 frame_estimate)."""
+    p = _sc16(iq, "iq", 5)
+    F, S, R, Cp, _ = iq.shape
+    _check(lib().ofdm_frame_combine_sc16(p, F, S, R, Cp - prefix, prefix, scale, _dptr(ws), ws.numel(), _dptr(out),
+                                         _stream(stream)), "ofdm_frame_combine_sc16")
+    return out
+
+
 def symbols_demod(sym, ws, prefix=0, frame=0, out=None, stream=None):
     """sym: (nsym, R, C+prefix) time-domain data symbols -> (nsym, K), against
     frame `frame`'s estimate in ws (filled by frame_estimate)."""
@@ -659,15 +727,24 @@ class Pipeline:
     """Streaming receiver over host-resident frames (ofdm_pipeline_*):
     `depth` device slots of `chunk_frames` frames, copy-in / compute /
     copy-out on three HIP streams.  demod() is asynchronous: keep `iq` and
-    `out` alive until sync()."""
+    `out` alive until sync().  sample_format "sc16": the frames are int16
+    (..., 2) arrays, x = i16 * scale, and the slots hold 4-byte samples
+    (ofdm_pipeline_create_sc16: half the bytes over the host link)."""
 
-    def __init__(self, S, R, C, X, prefix=0, chunk_frames=4, depth=3):
+    def __init__(self, S, R, C, X, prefix=0, chunk_frames=4, depth=3, sample_format="fc32", scale=SC16_SCALE):
+        if sample_format not in ("fc32", "sc16"):
+            raise OfdmError(f"sample_format must be 'fc32' or 'sc16', not {sample_format!r}")
         self.S, self.R, self.C, self.prefix = S, R, C, prefix
+        self.sc16 = sample_format == "sc16"
         Xp = X.data_ptr() if hasattr(X, "data_ptr") else np.ascontiguousarray(
             X, np.complex64).ctypes.data
         h = _P()
-        _check(lib().ofdm_pipeline_create(S, R, C, prefix, _P(Xp), chunk_frames, depth,
-                                          _c.byref(h)), "ofdm_pipeline_create")
+        if self.sc16:
+            _check(lib().ofdm_pipeline_create_sc16(S, R, C, prefix, scale, _P(Xp), chunk_frames, depth,
+                                                   _c.byref(h)), "ofdm_pipeline_create_sc16")
+        else:
+            _check(lib().ofdm_pipeline_create(S, R, C, prefix, _P(Xp), chunk_frames, depth,
+                                              _c.byref(h)), "ofdm_pipeline_create")
         self._h = h
 
     @staticmethod
@@ -675,11 +752,18 @@ class Pipeline:
         return _P(a.data_ptr() if hasattr(a, "data_ptr") else a.ctypes.data)
 
     def demod(self, iq, out):
-        """iq: (F, S, R, C+prefix) complex64, out: (F, S-1, K) complex64 --
-        numpy arrays or tensors (host or device), contiguous."""
+        """iq: (F, S, R, C+prefix) complex64 -- for an sc16 pipeline
+        (F, S, R, C+prefix, 2) int16 --, out: (F, S-1, K) complex64: numpy
+        arrays or tensors (host or device), contiguous."""
         F = iq.shape[0]
-        assert tuple(iq.shape[1:]) == (self.S, self.R, self.C + self.prefix), iq.shape
         assert tuple(out.shape) == (F, self.S - 1, self.C - 1), out.shape
+        if self.sc16:
+            assert tuple(iq.shape[1:]) == (self.S, self.R, self.C + self.prefix, 2), iq.shape
+            assert str(iq.dtype).endswith("int16"), iq.dtype
+            _check(lib().ofdm_pipeline_demod_sc16(self._h, self._ptr(iq), F, self._ptr(out)),
+                   "ofdm_pipeline_demod_sc16")
+            return out
+        assert tuple(iq.shape[1:]) == (self.S, self.R, self.C + self.prefix), iq.shape
         _check(lib().ofdm_pipeline_demod(self._h, self._ptr(iq), F, self._ptr(out)),
                "ofdm_pipeline_demod")
         return out
@@ -688,6 +772,12 @@ class Pipeline:
         d, s = _P(), _P()
         _check(lib().ofdm_pipeline_acquire(self._h, _c.byref(d), _c.byref(s)),
                "ofdm_pipeline_acquire")
+        return d.value, s.value
+
+    def acquire_sc16(self):
+        d, s = _P(), _P()
+        _check(lib().ofdm_pipeline_acquire_sc16(self._h, _c.byref(d), _c.byref(s)),
+               "ofdm_pipeline_acquire_sc16")
         return d.value, s.value
 
     def submit(self, nframes, out=None):

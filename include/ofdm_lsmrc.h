@@ -32,6 +32,7 @@
 #define OFDM_LSMRC_H_
 
 #include <stddef.h>
+#include <stdint.h>
 
 #ifdef __cplusplus
 extern "C" {
@@ -42,6 +43,10 @@ extern "C" {
 #define OFDM_LSMRC_VERSION 2
 
 typedef struct ofdm_cf32 { float re, im; } ofdm_cf32;
+/* One sc16 sample, 4 bytes: re in the low half of the little-endian dword --
+ * std::complex<int16_t>, what a UHD rx_streamer delivers for the cpu format
+ * "sc16" (see "sc16 IQ" below). */
+typedef struct ofdm_sc16 { int16_t re, im; } ofdm_sc16;
 typedef void *ofdm_stream_t; /* hipStream_t */
 
 enum {
@@ -394,6 +399,63 @@ int ofdm_pipeline_sync(ofdm_pipeline *p);
 /* Page-lock / release a host range for asynchronous DMA (hipHostRegister). */
 int ofdm_host_register(void *p, size_t bytes);
 int ofdm_host_unregister(void *p);
+
+/* ------------------------------------------------------------ sc16 IQ --- */
+
+/* Frames as the radios deliver them (no version step: OFDM_LSMRC_VERSION
+ * stays 2).  The reference's drivers default the over-the-wire format to
+ * sc16 (rx_and_corr.cpp:112,283, tx_same_seq_no_udp.cpp:108) and have UHD
+ * widen every sample to fc32 on the host CPU (stream_args_t("fc32", otw))
+ * before it enters the ring; the entries below take the 4-byte samples
+ * themselves, so a host-fed receiver moves half the bytes over PCIe, keeps
+ * half the IQ in HBM, and the radio process converts nothing.
+ *
+ * Layout: today's [nframes][S][R][C + cp_len], the element an ofdm_sc16.
+ * Semantics: every *_sc16 entry is DEFINED as its fp32 counterpart applied to
+ *     x = (float)i16 * scale        per component,
+ * scale finite and > 0 (else OFDM_E_ARG): 1.0f / 32767 is UHD's convention,
+ * 2^-15 the power of two.  Results agree with that definition to f32
+ * rounding (the scale may be applied after the transform, which is linear);
+ * the demodulated output does not depend on scale, the estimate does: Hconj
+ * and Hsqrd in the workspace are in the units of x.
+ *
+ * ofdm_iq_convert_sc16: d_out[i] = {(float)re * scale, (float)im * scale}
+ *     for n samples, one rounding each -- bit-exact for any scale.  d_in and
+ *     d_out 16-B aligned; n == 0 is a no-op.  It is the route for every FFT
+ *     length without an sc16 receiver: convert, then call any fp32 entry.
+ * ofdm_frame_estimate_sc16 / _combine_sc16 / _demod_sc16: the two-launch
+ *     C = 1024 receiver (ofdm_frame_estimate, ofdm_frame_combine, and
+ *     ofdm_frame_demod_ex(OFDM_FLOW_TWO_LAUNCH)) instantiated on the sample
+ *     type: each IQ row is read once, as 4 KiB.  Any other valid C returns
+ *     OFDM_E_UNSUPPORTED before any device work (use ofdm_iq_convert_sc16).
+ *     d_iq 16-B aligned; rows need 4-byte alignment only, so any cp_len
+ *     works.  The workspace is the fp32 one (ofdm_frame_workspace_bytes, same
+ *     layout, same registry rules), so ofdm_frame_export_estimate,
+ *     ofdm_frame_noise_estimate, ofdm_frame_soft_demap and the fp32
+ *     ofdm_frame_combine work on an sc16 estimate, and ofdm_frame_combine_sc16
+ *     on an fp32 one.  The sticky device status is consulted as in the fp32
+ *     entries.
+ * ofdm_pipeline_create_sc16: an ofdm_pipeline whose slots hold sc16, so the
+ *     host->device copy is half the bytes at every valid C.  At C = 1024 a
+ *     submit runs ofdm_frame_demod_sc16; at every other C each slot also owns
+ *     an fp32 buffer of chunk_frames frames (chunk_frames * S * R * (C +
+ *     cp_len) * 8 bytes of device memory per slot, on top of the 4-byte
+ *     slot), and a submit converts into it on the compute stream and runs
+ *     ofdm_frame_demod.  ofdm_pipeline_acquire_sc16 / _demod_sc16 are the
+ *     sc16 forms of acquire / demod; submit, sync and destroy are shared.
+ *     The fp32 acquire / demod on an sc16 pipeline, and the sc16 ones on an
+ *     fp32 pipeline, return OFDM_E_ARG. */
+int ofdm_iq_convert_sc16(const ofdm_sc16 *d_in, long long n, float scale, ofdm_cf32 *d_out, ofdm_stream_t stream);
+int ofdm_frame_demod_sc16(const ofdm_sc16 *d_iq, long long nframes, int S, int R, int C, int cp_len, float scale,
+                          const ofdm_cf32 *d_X, void *d_ws, size_t ws_bytes, ofdm_cf32 *d_out, ofdm_stream_t stream);
+int ofdm_frame_estimate_sc16(const ofdm_sc16 *d_iq, long long nframes, int S, int R, int C, int cp_len, float scale,
+                             const ofdm_cf32 *d_X, void *d_ws, size_t ws_bytes, ofdm_stream_t stream);
+int ofdm_frame_combine_sc16(const ofdm_sc16 *d_iq, long long nframes, int S, int R, int C, int cp_len, float scale,
+                            void *d_ws, size_t ws_bytes, ofdm_cf32 *d_out, ofdm_stream_t stream);
+int ofdm_pipeline_create_sc16(int S, int R, int C, int cp_len, float scale, const ofdm_cf32 *X, int chunk_frames,
+                              int depth, ofdm_pipeline **out);
+int ofdm_pipeline_acquire_sc16(ofdm_pipeline *p, ofdm_sc16 **d_iq, ofdm_stream_t *copy_stream);
+int ofdm_pipeline_demod_sc16(ofdm_pipeline *p, const ofdm_sc16 *iq, long long nframes, ofdm_cf32 *out);
 
 /* ------------------------------------------------------ PN frame sync --- */
 
