@@ -144,17 +144,22 @@ static hipError_t synth_t(float2 *iq, long long nframes, int S, int R, int prefi
     const int threads = C / 4 < 256 ? (C / 4 < 64 ? 64 : C / 4) : 256;
     const size_t lds = 2 * C * sizeof(float2);
     const long long rows = nframes * S * R;
-    const long long maxg = 1ll << 30;
+    // a launch holds fewer than 2^32 threads (HIP refuses gridDim.x * blockDim.x
+    // beyond that, and the launches after it would hide its error)
+    const long long maxg = 0xffffffffll / threads;
     const long long Cp = freq_domain ? C : C + prefix;
-    for (long long q0 = 0; q0 < rows; q0 += maxg) {
-        // chunk boundaries must be whole frames for the index math
-        long long n = rows - q0 < maxg ? rows - q0 : maxg;
-        const long long frame_rows = (long long)S * R;
+    const long long frame_rows = (long long)S * R;
+    if (frame_rows > maxg) return hipErrorInvalidValue;
+    // chunk boundaries must be whole frames for the index math: a launch takes
+    // the whole frames that fit and the next one starts where it ended
+    for (long long q0 = 0, n = 0; q0 < rows; q0 += n) {
+        n = rows - q0 < maxg ? rows - q0 : maxg;
         n = (n / frame_rows) * frame_rows;
         hipLaunchKernelGGL(k_synth<LOG2C>, dim3((unsigned)n), dim3(threads), lds, s, iq + q0 * Cp, S,
                            R, prefix, X, seed, frame0 + q0 / frame_rows, noise_std, freq_domain, r0);
+        if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
     }
-    return hipGetLastError();
+    return hipSuccess;
 }
 
 // Any other C (fft_any.hip sizes): the same frames in three passes over the
