@@ -833,6 +833,29 @@ int ofdm_frame_export_estimate(const void *d_ws, size_t ws_bytes_, long long nfr
                      "ofdm_frame_export_estimate");
 }
 
+int ofdm_frame_estimate_denoise(void *d_ws, size_t ws_bytes_, long long nframes, int S, int R, int C, int taps_post,
+                                int taps_pre, ofdm_stream_t stream) {
+    static const char *fn = "ofdm_frame_estimate_denoise";
+    if (nframes < 0) return fail(OFDM_E_ARG, "%s: nframes < 0", fn);
+    if (S < 2 || R < 1 || !valid_c(C))
+        return fail(OFDM_E_ARG, "%s: bad geometry (S=%d >= 2, R=%d >= 1, 2 <= C=%d <= 8192)", fn, S, R, C);
+    if (taps_post < 1 || taps_pre < 0 || taps_post > C - taps_pre)
+        return fail(OFDM_E_ARG, "%s: taps_post=%d, taps_pre=%d: taps_post >= 1, taps_pre >= 0 and "
+                                "taps_post + taps_pre <= C=%d required", fn, taps_post, taps_pre, C);
+    if (nframes == 0) return OFDM_OK;
+    if (!d_ws) return fail(OFDM_E_ARG, "%s: null workspace", fn);
+    // a full estimate of this geometry, of any estimator: the tag says which layout.  No work tickets,
+    // no sticky status; the registry entry stays as it is (the denoised estimate serves every consumer).
+    WsTag tag;
+    int rc = ws_check(d_ws, ws_bytes_, nframes, S, R, C, true, fn, &tag);
+    if (rc) return rc;
+    Workspace w;
+    if ((rc = carve(d_ws, ws_bytes_, nframes, S, R, C, !fused_c(C), w))) return rc;
+    return hip_check(ofdm::launch_estimate_denoise(w.Hc, w.P, nframes, R, C, tag.lane_order, taps_post, taps_pre,
+                                                   hs(stream)),
+                     fn);
+}
+
 // Soft output: what both calls check before any device work, then the
 // registry (a full estimate of this geometry, time- or frequency-domain: P is
 // bin-indexed in all of them).  Returns 1 for the nframes == 0 no-op.

@@ -2,7 +2,8 @@
 // ANY length C in [2, 8192] (k_fft_any) and the fused any-C MRC (k_mrc_any:
 // FFT + combine + normalise + rotate in one HBM pass) and the any-C OFDM
 // modulator (k_tx_any: bin placement + backward FFT + peak + scale + cyclic
-// prefix in one HBM pass; ofdm_tx_modulate), for the sizes the
+// prefix in one HBM pass; ofdm_tx_modulate) and the delay-domain denoising of
+// the workspace estimate (k_denoise_any; every C), for the sizes the
 // power-of-two kernels (k_fft_rows, the fused C = 1024 / 2048 / 4096
 // receivers) do not cover: 1536 (LTE 15 MHz), 3072, 6144, 600, 1200, odd and
 // prime lengths, 8192 and the small powers of two.  The reference transforms
@@ -34,6 +35,7 @@
 // CU), 8192 (512 threads, 128 KiB, 1 per CU); each thread holds CAP / NT
 // elements of a prefetched row group.
 #include "common.hpp"
+#include "lane_layout.hpp"
 #include "launch.hpp"
 #include "pk.hpp"
 #include "tx_map.hpp"
@@ -361,6 +363,127 @@ k_tx_any(const float2 *__restrict__ X, long long ldx, long long nrows, int cp, i
     }
 }
 
+// Delay-domain denoising of the workspace estimate for any C
+// (ofdm_frame_estimate_denoise), in place: one workgroup per frame, the
+// frame's R rows in order of r in groups of G.  A group arrives in registers
+// (coalesced, prefetched during the previous group's stages) and goes to LDS
+// by position; the rows are gathered through hc_pos (a table in LDS) into bin
+// order as H[b] = conj(Hc[b]) with H[0] = (H[1] + H[C-1]) / 2, the stages run
+// backward, the taps outside [0, taps_post) u [C - taps_pre, C) are zeroed
+// (the kept ones scaled by 1/C), the stages run forward, and conj(H') goes
+// back through hc_pos into the free buffer, from where the group is stored
+// coalesced -- all but the bin-0 position of each row, which is never
+// written.  A thread owns the bins t + j NT of every row and adds their
+// |H'|^2 in order of r: P' needs no atomics and is the same in every run.
+// layC: the C whose lane order the rows are in, 0 for the bin layout.
+template <int CAP, int NT = nt_of(CAP)>
+__global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(wpe_of(CAP), wpe_of(CAP))))
+k_denoise_any(float2 *__restrict__ Hc, float *__restrict__ P, long long nframes, int R, int layC, int taps_post,
+              int taps_pre, Plan plan) {
+    constexpr int MAXE = CAP / NT;
+    __shared__ float2 x0[CAP], x1[CAP], lo[TLO], hi[THI];
+    // hc_pos of every bin, once per workgroup instead of twice per element
+    // (measured: 7 - 12 % of the kernel's time at C = 1536 ... 4096)
+    __shared__ unsigned short pos[CAP];
+    static_assert((CAP == 2048 ? 4 : CAP == 4096 ? 2 : 1) * (sizeof(float2) * (2 * CAP + TLO + THI) + 2 * CAP) <=
+                      160 * 1024, "the resident workgroups (resident()) fit the CU's 160 KiB of LDS");
+    const unsigned C = (unsigned)plan.C, G = (unsigned)plan.G;
+    fill_tables<NT>(lo, hi, C);
+    for (unsigned b = threadIdx.x; b < C; b += NT) pos[b] = (unsigned short)lane::hc_pos(layC, (int)b);
+    const Tw T{lo, hi};
+    const int ngr = (R + (int)G - 1) / (int)G;
+    const float inv = 1.f / (float)C;
+    const unsigned keep_lo = (unsigned)taps_post, keep_hi = C - (unsigned)taps_pre;
+    const unsigned pos0 = (unsigned)lane::hc_pos(layC, 0), pos1 = (unsigned)lane::hc_pos(layC, 1),
+                   posm = (unsigned)lane::hc_pos(layC, (int)C - 1);
+    auto rows_in = [&](int g) { return (unsigned)(R - g * (int)G < (int)G ? R - g * (int)G : (int)G); };
+    auto rows_at = [&](long long f, int g) { return Hc + (f * R + (long long)g * G) * C; };
+    float2 pf[MAXE];
+    float acc[MAXE];
+    // a group's rows are contiguous: element e = t + i NT of n * C
+    auto load_group = [&](long long f, int g) {
+        const float2 *src = rows_at(f, g);
+        const unsigned ne = rows_in(g) * C;
+#pragma unroll
+        for (int i = 0; i < MAXE; ++i) {
+            const unsigned e = tid_here() + i * NT;
+            pf[i] = float2{0.f, 0.f};
+            if (e < ne) pf[i] = src[e];
+        }
+    };
+#pragma unroll
+    for (int j = 0; j < MAXE; ++j) acc[j] = 0.f;
+    long long f = blockIdx.x;
+    int gi = 0;
+    if (f < nframes) load_group(f, 0);
+    while (f < nframes) {
+        const unsigned n = rows_in(gi), ne = n * C;
+#pragma unroll
+        for (int i = 0; i < MAXE; ++i) x1[tid_here() + i * NT] = pf[i];
+        lds_sync();  // the group and, the first time, the twiddle and position tables
+        long long fn = f;
+        int gn = gi + 1;
+        if (gn == ngr) {
+            gn = 0;
+            fn = f + gridDim.x;
+        }
+        if (fn < nframes) load_group(fn, gn);
+        for (unsigned e = tid_here(); e < ne; e += NT) {
+            const unsigned g = fdiv(e, plan.dC), b = e - g * C;
+            const float2 *row = x1 + g * C;
+            float2 v;
+            if (b == 0) {
+                const float2 a = row[pos1], c = row[posm];
+                v = float2{0.5f * (a.x + c.x), -0.5f * (a.y + c.y)};
+            } else {
+                const float2 h = row[pos[b]];
+                v = float2{h.x, -h.y};
+            }
+            x0[e] = v;
+        }
+        lds_sync();
+        float2 *g0 = run_stages<NT, true>(x0, x1, T, plan, n, plan.ns);
+        float2 *g1 = g0 == x0 ? x1 : x0;
+        for (unsigned e = tid_here(); e < ne; e += NT) {
+            const unsigned g = fdiv(e, plan.dC), t = e - g * C;
+            const float2 v = g0[e];
+            g0[e] = (t < keep_lo || t >= keep_hi) ? float2{v.x * inv, v.y * inv} : float2{0.f, 0.f};
+        }
+        lds_sync();
+        const float2 *z = run_stages<NT, false>(g0, g1, T, plan, n, plan.ns);
+        float2 *w = z == x0 ? x1 : x0;
+#pragma unroll
+        for (int j = 0; j < MAXE; ++j) {
+            const unsigned b = tid_here() + j * NT;
+            if (b < C) {
+                const unsigned p = pos[b];
+                for (unsigned g = 0; g < n; ++g) {
+                    const float2 v = z[g * C + b];
+                    acc[j] += v.x * v.x + v.y * v.y;
+                    w[g * C + p] = float2{v.x, -v.y};
+                }
+            }
+        }
+        lds_sync();
+        float2 *dst = rows_at(f, gi);
+        for (unsigned e = tid_here(); e < ne; e += NT) {
+            const unsigned g = fdiv(e, plan.dC);
+            if (e - g * C != pos0) dst[e] = w[e];
+        }
+        if (gn == 0) {  // frame f complete
+#pragma unroll
+            for (int j = 0; j < MAXE; ++j) {
+                const unsigned b = tid_here() + j * NT;
+                if (b >= 1 && b < C) P[f * C + b] = acc[j];
+                acc[j] = 0.f;
+            }
+        }
+        lds_sync();  // the next group goes into x1
+        f = fn;
+        gi = gn;
+    }
+}
+
 // The last FFT stage fused with the combine: the stage's butterfly k1 (of
 // cp = C / P; Lp = cp, no output permutation left) yields bins k1 + cp k2,
 // k2 < P, of one row; each is multiplied by its channel estimate (bin-layout
@@ -644,6 +767,16 @@ hipError_t launch_tx_t(const float2 *X, long long ldx, long long nrows, int cp, 
 }
 
 template <int CAP>
+hipError_t launch_denoise_t(float2 *Hc, float *P, long long nframes, int R, int layC, int taps_post, int taps_pre,
+                            const Plan &pl, hipStream_t s) {
+    const long long res = resident(CAP);
+    const unsigned grid = (unsigned)(nframes < res ? nframes : res);  // persistent over the frames
+    hipLaunchKernelGGL((k_denoise_any<CAP>), dim3(grid), dim3(nt_of(CAP)), 0, s, Hc, P, nframes, R, layC, taps_post,
+                       taps_pre, pl);
+    return hipGetLastError();
+}
+
+template <int CAP>
 hipError_t launch_mrc_t(const float2 *iq, long long nframes, int S, int R, int prefix, const float2 *Hc,
                         const float *P, float2 *out, int mode, const Plan &pl, hipStream_t s) {
     const long long nq = nframes * (S - 1);
@@ -692,6 +825,20 @@ hipError_t launch_tx_any(const float2 *X, long long ldx, long long nrows, int C,
     case 2048: return fany::launch_tx_t<2048>(X, ldx, nrows, cp, map, norm, scale, iq, peak, pl, s);
     case 4096: return fany::launch_tx_t<4096>(X, ldx, nrows, cp, map, norm, scale, iq, peak, pl, s);
     default: return fany::launch_tx_t<8192>(X, ldx, nrows, cp, map, norm, scale, iq, peak, pl, s);
+    }
+}
+
+hipError_t launch_denoise_any(float2 *Hc, float *P, long long nframes, int R, int C, bool lane_order, int taps_post,
+                              int taps_pre, hipStream_t s) {
+    if (nframes <= 0) return hipSuccess;
+    fany::Plan pl;
+    if (!fany::make_plan(C, pl) || R < 1 || taps_post < 1 || taps_pre < 0 || taps_post > C - taps_pre)
+        return hipErrorInvalidValue;
+    const int layC = lane_order ? C : 0;
+    switch (fany::cap_of(C)) {
+    case 2048: return fany::launch_denoise_t<2048>(Hc, P, nframes, R, layC, taps_post, taps_pre, pl, s);
+    case 4096: return fany::launch_denoise_t<4096>(Hc, P, nframes, R, layC, taps_post, taps_pre, pl, s);
+    default: return fany::launch_denoise_t<8192>(Hc, P, nframes, R, layC, taps_post, taps_pre, pl, s);
     }
 }
 

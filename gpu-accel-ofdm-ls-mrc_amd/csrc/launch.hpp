@@ -178,6 +178,19 @@ hipError_t launch_dist_sqrd(const float2 *H, int R, int K, float *P, hipStream_t
 hipError_t launch_export_estimate(const float2 *Hc, const float *P, int R, int C, bool lane_order,
                                   float2 *Hconj, float *Hsqrd, hipStream_t s);
 
+// Delay-domain denoising of the workspace estimate, in place
+// (est_denoise.hip; ofdm_frame_estimate_denoise states the operation): Hc
+// [nframes][R][C] rows in C's lane order (lane_order) or in bin layout, P
+// [nframes][C] bin-indexed.  The bin-0 position of every row keeps its bits
+// and P[f][0] is not written.  1 <= taps_post, 0 <= taps_pre, taps_post +
+// taps_pre <= C.  C = 1024 in lane order runs the wave kernel k_denoise1024,
+// everything else launch_denoise_any (fft_any.hip k_denoise_any: any C and
+// either layout).
+hipError_t launch_estimate_denoise(float2 *Hc, float *P, long long nframes, int R, int C, bool lane_order,
+                                   int taps_post, int taps_pre, hipStream_t s);
+hipError_t launch_denoise_any(float2 *Hc, float *P, long long nframes, int R, int C, bool lane_order, int taps_post,
+                              int taps_pre, hipStream_t s);
+
 // Soft output (soft_demap.hip).  z: the demodulated [nframes][S-1][K] array
 // (16-B aligned), P: the workspace's bin-indexed |H|^2 [nframes][C], bps in
 // {2, 4, 6, 8}.  noise_estimate: nv[f] = mean of P |Z - slice(Z)|^2 over frame

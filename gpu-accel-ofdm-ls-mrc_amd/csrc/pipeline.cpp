@@ -38,6 +38,7 @@ struct ofdm_pipeline {
     int S = 0, R = 0, C = 0, cp = 0, K = 0, device = 0;
     bool sc16 = false;  // the slots hold ofdm_sc16 samples, x = i16 * scale
     float scale = 1.f;
+    int taps_post = 0, taps_pre = 0;  // ofdm_pipeline_set_denoise; taps_post == 0: off
     long long chunk = 0;
     size_t ws_bytes = 0, frame_in = 0, frame_out = 0;  // elements
     ofdm_cf32 *X = nullptr;
@@ -257,7 +258,26 @@ int ofdm_pipeline_submit(ofdm_pipeline *p, long long nframes, ofdm_cf32 *out) {
     rel.enqueued = true;
     PL_TRY(hipStreamWaitEvent(p->s_comp, s.in_done, 0), fn, "hipStreamWaitEvent");
     if (s.used) PL_TRY(hipStreamWaitEvent(p->s_comp, s.out_done, 0), fn, "hipStreamWaitEvent");
-    if (nframes > 0) {
+    if (nframes > 0 && p->taps_post > 0) {
+        // estimate -> denoise -> combine (the one-launch demod cannot take the denoising in)
+        const bool sc = p->sc16 && !s.f32;
+        const ofdm_cf32 *iq = static_cast<const ofdm_cf32 *>(s.f32 ? s.f32 : s.iq);
+        const ofdm_sc16 *iq16 = static_cast<const ofdm_sc16 *>(s.iq);
+        int rc = OFDM_OK;
+        if (s.f32) rc = ofdm_iq_convert_sc16(iq16, (long long)(nframes * p->frame_in), p->scale, s.f32, p->s_comp);
+        if (rc == OFDM_OK)
+            rc = sc ? ofdm_frame_estimate_sc16(iq16, nframes, p->S, p->R, p->C, p->cp, p->scale, p->X, s.ws,
+                                               p->ws_bytes, p->s_comp)
+                    : ofdm_frame_estimate(iq, nframes, p->S, p->R, p->C, p->cp, p->X, s.ws, p->ws_bytes, p->s_comp);
+        if (rc == OFDM_OK)
+            rc = ofdm_frame_estimate_denoise(s.ws, p->ws_bytes, nframes, p->S, p->R, p->C, p->taps_post, p->taps_pre,
+                                             p->s_comp);
+        if (rc == OFDM_OK)
+            rc = sc ? ofdm_frame_combine_sc16(iq16, nframes, p->S, p->R, p->C, p->cp, p->scale, s.ws, p->ws_bytes,
+                                              s.out, p->s_comp)
+                    : ofdm_frame_combine(iq, nframes, p->S, p->R, p->C, p->cp, s.ws, p->ws_bytes, s.out, p->s_comp);
+        if (rc) return rc;
+    } else if (nframes > 0) {
         int rc;
         if (!p->sc16) {
             rc = ofdm_frame_demod(static_cast<const ofdm_cf32 *>(s.iq), nframes, p->S, p->R, p->C, p->cp, p->X, s.ws,
@@ -285,6 +305,17 @@ int ofdm_pipeline_submit(ofdm_pipeline *p, long long nframes, ofdm_cf32 *out) {
     s.used = true;
     s.acquired = false;
     p->next = (p->next + 1) % (int)p->slots.size();
+    return OFDM_OK;
+}
+
+int ofdm_pipeline_set_denoise(ofdm_pipeline *p, int taps_post, int taps_pre) {
+    static const char *fn = "ofdm_pipeline_set_denoise";
+    if (!p) return err(OFDM_E_ARG, fn, "null pipeline");
+    if (taps_post < 0 || taps_pre < 0) return err(OFDM_E_ARG, fn, "taps_post >= 0 and taps_pre >= 0 required");
+    if (taps_post == 0 && taps_pre != 0) return err(OFDM_E_ARG, fn, "taps_post == 0 (off) takes taps_pre == 0");
+    if (taps_post > p->C - taps_pre) return err(OFDM_E_ARG, fn, "taps_post + taps_pre exceeds C");
+    p->taps_post = taps_post;
+    p->taps_pre = taps_pre;
     return OFDM_OK;
 }
 

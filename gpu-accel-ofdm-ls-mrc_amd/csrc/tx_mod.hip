@@ -19,14 +19,9 @@ using namespace td1024;
 
 constexpr int WAVES = 8;  // rows per workgroup pass; LDS 9.0 + 8 x 8.5 KiB: two workgroups per CU
 
-// Natural-order image of a finished row in the wave's transpose region:
-// sample n at row n >> 6 (pitch TP), column (n & 63) rotated by 4 (n >> 8).
-// The rotation puts the four rows a lane quad writes at once (n = q + 256 c
-// + 16 k: rows 4 c + (k >> 2), 4 x 544 B apart = the same bank) on four
-// different bank groups, so the 16 ds_write_b64 of a row are conflict free;
-// it is a multiple of two samples, so an even n and n + 1 stay one aligned
-// 16-B word for the wide store path.
-__device__ __forceinline__ int img(int n) { return (n >> 6) * TP + (((n & 63) + 4 * (n >> 8)) & 63); }
+// The finished row goes through the natural-order image of wave_fft1024.hpp
+// (nat_img): conflict-free writes from row_fft's output order, and an even n and
+// n + 1 in one aligned 16-B word for the wide store path.
 
 typedef float f4v __attribute__((ext_vector_type(4)));
 
@@ -65,19 +60,19 @@ k_tx_mod1024(const float2 *__restrict__ X, long long ldx, long long nrows, int c
         const float s = tx_gain(pk, norm, scale);
         const int b0 = lane_bin0(t);
 #pragma unroll
-        for (int k = 0; k < 16; ++k) T[img(b0 + 16 * k)] = float2{x[k].y * s, x[k].x * s};
+        for (int k = 0; k < 16; ++k) T[nat_img(b0 + 16 * k)] = float2{x[k].y * s, x[k].x * s};
         wave_lds_sync();
         float2 *o = iq + row * Cp;
         if (WIDE) {  // output samples 2 i, 2 i + 1 = row samples n, n + 1, n = (2 i - cp) mod C even
             const int np = Cp >> 1;
             for (int i = t; i < np; i += 64) {
                 const int n = (2 * i + C - cp) & (C - 1);
-                const float4 v = *reinterpret_cast<const float4 *>(T + img(n));
+                const float4 v = *reinterpret_cast<const float4 *>(T + nat_img(n));
                 __builtin_nontemporal_store(f4v{v.x, v.y, v.z, v.w}, reinterpret_cast<f4v *>(o + 2 * i));
             }
         } else {
             for (int e = t; e < Cp; e += 64) {
-                const float2 v = T[img((e + C - cp) & (C - 1))];
+                const float2 v = T[nat_img((e + C - cp) & (C - 1))];
                 __builtin_nontemporal_store(__builtin_bit_cast(unsigned long long, v),
                                             reinterpret_cast<unsigned long long *>(o + e));
             }

@@ -226,6 +226,18 @@ __device__ __forceinline__ int lane_bin0(int t) {
     return (t >> 2) + 256 * ((qa >> 1) + 2 * (qa & 1));
 }
 
+// Natural-order image of a row in the wave's transpose region (the
+// modulator's finished row, the estimate denoiser's re-orderings from
+// row_fft's output order to its input order): sample n at row n >> 6 (pitch
+// TP), column (n & 63) rotated by 4 (n >> 8).  The rotation puts the four
+// rows a lane quad writes at once (n = q + 256 c + 16 k: rows 4 c + (k >> 2),
+// 4 x 544 B apart = the same bank) on four different bank groups, so the 16
+// ds_write_b64 of a row in row_fft's output order are conflict free; it is a
+// multiple of two samples, so an even n and n + 1 stay one aligned 16-B word.
+// A read of nat_img(t + 64 m) over the lanes t is one image row, 64 consecutive
+// (rotated) 8-B words: conflict free as well.
+__device__ __forceinline__ int nat_img(int n) { return (n >> 6) * TP + (((n & 63) + 4 * (n >> 8)) & 63); }
+
 // Channel estimates of one (frame, antenna row) in "lane order": the 16 bins
 // lane t owns (b0(t) + 16 k) as 8 float4 pairs, pair i of lane t at float4
 // index i*64 + t -- one contiguous 1 KiB wave load per pair.  Same 8 KiB per

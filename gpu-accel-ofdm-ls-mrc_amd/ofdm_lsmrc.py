@@ -59,6 +59,7 @@ _SIGS = {
     "ofdm_frame_mrc_partial": (_I, [_P, _LL, _I, _I, _I, _I, _P, _c.c_size_t, _P, _P]),
     "ofdm_frame_mrc_partial_range": (_I, [_P, _LL, _LL, _LL, _I, _I, _I, _I, _P, _c.c_size_t, _P, _P]),
     "ofdm_frame_export_estimate": (_I, [_P, _c.c_size_t, _LL, _I, _I, _I, _LL, _P, _P, _P]),
+    "ofdm_frame_estimate_denoise": (_I, [_P, _c.c_size_t, _LL, _I, _I, _I, _I, _I, _P]),
     "ofdm_frame_noise_estimate": (_I, [_P, _LL, _I, _I, _I, _P, _c.c_size_t, _I, _P, _P]),
     "ofdm_frame_soft_demap": (_I, [_P, _LL, _I, _I, _I, _P, _c.c_size_t, _I, _P, _I, _c.c_float, _P, _P]),
     "ofdm_symbols_demod": (_I, [_P, _LL, _I, _I, _I, _P, _c.c_size_t, _LL, _P, _P]),
@@ -71,6 +72,7 @@ _SIGS = {
     "ofdm_pipeline_submit": (_I, [_P, _LL, _P]),
     "ofdm_pipeline_demod": (_I, [_P, _P, _LL, _P]),
     "ofdm_pipeline_sync": (_I, [_P]),
+    "ofdm_pipeline_set_denoise": (_I, [_P, _I, _I]),
     "ofdm_iq_convert_sc16": (_I, [_P, _LL, _c.c_float, _P, _P]),
     "ofdm_frame_demod_sc16": (_I, [_P, _LL, _I, _I, _I, _I, _c.c_float, _P, _P, _c.c_size_t, _P, _P]),
     "ofdm_frame_estimate_sc16": (_I, [_P, _LL, _I, _I, _I, _I, _c.c_float, _P, _P, _c.c_size_t, _P]),
@@ -537,6 +539,15 @@ def frame_export_estimate(ws, F, S, R, C, frame=0, stream=None):
     return H, P
 
 
+def frame_estimate_denoise(ws, F, S, R, C, taps_post, taps_pre=0, stream=None):
+    """Delay-domain denoising of the estimate in ws (any full estimate of this
+    F, S, R, C), in place: the taps [0, taps_post) and [C - taps_pre, C) of
+    every antenna's channel are kept, the rest zeroed (include/ofdm_lsmrc.h)."""
+    _check(lib().ofdm_frame_estimate_denoise(_dptr(ws, "ws") if F else None, ws.numel() if F else 0, F, S, R, C,
+                                             taps_post, taps_pre, _stream(stream)), "ofdm_frame_estimate_denoise")
+    return ws
+
+
 MOD_QPSK, MOD_QAM16, MOD_QAM64, MOD_QAM256 = 2, 4, 6, 8  # OFDM_MOD_*: bits per symbol
 _LLR_FORMATS = {"f32": 0, "i8": 1}  # OFDM_LLR_*
 
@@ -787,6 +798,11 @@ class Pipeline:
 
     def sync(self):
         _check(lib().ofdm_pipeline_sync(self._h), "ofdm_pipeline_sync")
+
+    def set_denoise(self, taps_post, taps_pre=0):
+        """Later submits run estimate -> frame_estimate_denoise -> combine;
+        taps_post = 0 turns it off again (the default)."""
+        _check(lib().ofdm_pipeline_set_denoise(self._h, taps_post, taps_pre), "ofdm_pipeline_set_denoise")
 
     def close(self):
         if getattr(self, "_h", None):

@@ -245,6 +245,41 @@ int ofdm_frame_combine(const ofdm_cf32 *d_iq, long long nframes, int S, int R, i
 int ofdm_frame_export_estimate(const void *d_ws, size_t ws_bytes, long long nframes, int S, int R, int C,
                                long long frame, ofdm_cf32 *d_Hconj, float *d_Hsqrd, ofdm_stream_t stream);
 
+/* Delay-domain denoising of the kept LS estimate (no reference counterpart;
+ * added without a version step: OFDM_LSMRC_VERSION stays 2).  The raw LS
+ * estimate carries a data bin's worth of noise in every bin; a channel no
+ * longer than the cyclic prefix occupies few taps, so the taps that cannot
+ * hold channel energy are zeroed and the estimate's noise falls by (kept
+ * taps) / C.  In place on a workspace that holds a FULL estimate of the same
+ * nframes, S, R, C, ws_bytes, of any estimator (ofdm_frame_estimate, _demod,
+ * _estimate_sc16, _demod_sc16, _estimate_freq, _demod_freq, _demod_freq_mfma;
+ * lane order or bin layout).  For each frame f and antenna r, with
+ * H[b] = conj(Hconj[b]) for the FFT bins b = 1 .. C-1 (the receivers drop
+ * bin 0):
+ *   1. H[0] := (H[1] + H[C-1]) / 2        (the one bin the pilot does not cover)
+ *   2. g[n]  = (1/C) sum_b H[b] e^{+2 pi i b n / C},  n = 0 .. C-1
+ *   3. g[n] := 0 unless n in [0, taps_post) or n in [C - taps_pre, C)
+ *      (the pre-cursor taps hold the channel when frame sync put the FFT
+ *      window inside the prefix)
+ *   4. H'[b] = sum_n g[n] e^{-2 pi i b n / C}
+ *   5. Hconj[b] := conj(H'[b]) and Hsqrd[f][b] := sum_r |H'[r][b]|^2 for
+ *      b = 1 .. C-1, the sum in order of r (no atomics: bit-identical from
+ *      run to run).
+ * The bin-0 position of every row and Hsqrd[f][0] stay as the estimator left
+ * them, as do the workspace's flags and ticket area and its registry entry:
+ * ofdm_frame_combine, _combine_sc16, _combine_freq, ofdm_symbols_demod,
+ * ofdm_frame_export_estimate, ofdm_frame_noise_estimate and
+ * ofdm_frame_soft_demap take the denoised workspace as they take a raw one.
+ * No work tickets; the sticky device status is neither consulted nor cleared.
+ * OFDM_E_ARG, before any device work: a null workspace with nframes > 0, bad
+ * geometry (S < 2, R < 1, C outside [2, 8192], nframes < 0), a workspace with
+ * no estimate or one of another geometry, an antenna-split partial estimate
+ * (ofdm_frame_ls_partial), taps_post < 1, taps_pre < 0 or taps_post + taps_pre
+ * > C.  nframes == 0 is a no-op (OFDM_OK).  taps_post + taps_pre == C keeps
+ * every tap: the kernels run and return the estimate to f32 rounding. */
+int ofdm_frame_estimate_denoise(void *d_ws, size_t ws_bytes, long long nframes, int S, int R, int C,
+                                int taps_post, int taps_pre, ofdm_stream_t stream);
+
 /* Soft-decision output (no reference counterpart; added without a version
  * step: OFDM_LSMRC_VERSION stays 2).  Both calls read d_z, the demodulated
  * [nframes][S-1][K] array of a frame call (rotated order, 16-B aligned), and
@@ -380,6 +415,15 @@ int ofdm_frame_mrc_partial_range(const ofdm_cf32 *d_iq, long long nframes, long 
  *       NULL = leave them in the slot) on the output stream.
  *   ofdm_pipeline_demod: acquire + copy + submit over nframes host frames.
  *   ofdm_pipeline_sync: waits for everything submitted.
+ *   ofdm_pipeline_set_denoise: with taps_post > 0 every later submit runs
+ *       estimate -> ofdm_frame_estimate_denoise(taps_post, taps_pre) ->
+ *       combine on the compute stream instead of ofdm_frame_demod (the sc16
+ *       forms on an sc16 pipeline at C = 1024; at another C the chunk is
+ *       converted and the fp32 forms run).  taps_post == 0 (with taps_pre ==
+ *       0) turns it off, the state of a new pipeline: a submit then enqueues
+ *       exactly what it enqueues without this call.  OFDM_E_ARG for a null
+ *       pipeline, a negative value, taps_pre without taps_post, or taps_post +
+ *       taps_pre > C.
  * Each call makes the pipeline's device current and restores the caller's
  * current device before returning.  A failed submit releases its slot (those
  * frames are not demodulated); the pipeline stays usable.
@@ -395,6 +439,7 @@ int ofdm_pipeline_submit(ofdm_pipeline *p, long long nframes, ofdm_cf32 *out);
 int ofdm_pipeline_demod(ofdm_pipeline *p, const ofdm_cf32 *iq, long long nframes,
                         ofdm_cf32 *out);
 int ofdm_pipeline_sync(ofdm_pipeline *p);
+int ofdm_pipeline_set_denoise(ofdm_pipeline *p, int taps_post, int taps_pre);
 
 /* Page-lock / release a host range for asynchronous DMA (hipHostRegister). */
 int ofdm_host_register(void *p, size_t bytes);
