@@ -14,6 +14,9 @@ exact DFT (float64, rounded to float32), which matches numpy/pocketfft.
 Each fixture .npz holds: iq (F,S,R,C+prefix) or yf (F,S,R,C) complex64,
 X (K,) complex64 rotated pilots, out (F,S-1,K) complex64, H (F,R,K), P (F,K),
 plus scalars R, C, S, prefix, seed, domain ('time'|'freq').
+
+A case may name a pilot family of tests/pilot_cases.py as its ninth field; its
+X is then pilot_cases.pilots(family, K, seed) instead of QPSK points.
 """
 import os
 import sys
@@ -22,6 +25,7 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
+import pilot_cases  # noqa: E402
 from oracle_bindings import Oracle, Reference  # noqa: E402
 
 CASES = [
@@ -36,6 +40,10 @@ CASES = [
     # round 4: configs[4]'s C (the wave-pair kernels k_ls_td4096 / k_mrc_td4096h)
     ("r8_c4096_s3_cp32", 1, 3, 8, 4096, 32, "time", 0.01),
     ("r32_c4096_s2", 1, 2, 32, 4096, 0, "time", 0.01),
+    # pilots of non-unit modulus (pilot_cases "boosted": 2^U(-1,1), any phase): the only fixtures in which
+    # divideOneRow divides by something other than 1
+    ("boosted_r4_c256_s3_cp8", 1, 3, 4, 256, 8, "time", 0.01, "boosted"),
+    ("boosted_freq_r3_c64_s3", 1, 3, 3, 64, 0, "freq", 0.01, "boosted"),
 ]
 
 
@@ -44,10 +52,13 @@ def qpsk(rng, shape):
     return (rng.choice([-a, a], shape) + 1j * rng.choice([-a, a], shape)).astype(np.complex64)
 
 
-def make_case(o, ref, name, F, S, R, C, prefix, domain, noise, seed, raw_pilots_path):
+def make_case(o, ref, name, F, S, R, C, prefix, domain, noise, family=None, *, seed, raw_pilots_path):
     rng = np.random.default_rng(seed)
     K = C - 1
-    X = ref.matrix_readX(raw_pilots_path, K) if C == 1024 else o.pilot_rotate(qpsk(rng, K))
+    if family:
+        X = pilot_cases.pilots(family, K, seed)
+    else:
+        X = ref.matrix_readX(raw_pilots_path, K) if C == 1024 else o.pilot_rotate(qpsk(rng, K))
     iq = []
     outs, Hs, Ps = [], [], []
     for f in range(F):
