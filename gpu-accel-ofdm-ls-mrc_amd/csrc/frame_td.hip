@@ -149,7 +149,8 @@ __device__ __forceinline__ void mac(float2 &acc, float2 x, float vx, float vy) {
 }
 
 
-// One antenna row of the prefetching loop: a[] holds this row on entry and
+// One antenna row of the sc16 loop (one row buffer; the fp32 rows are
+// hlds_row_pp's): a[] holds this row on entry and
 // the next row (`next`, when PREF) on exit.  The thread's 16 B of the Hc row
 // are a buffer load -- hc: the frame's estimates, hoff: the byte offset of
 // (row, this wave's 1 KiB), in SGPRs; the lane's offset is formed here -- so
@@ -194,10 +195,70 @@ __device__ __forceinline__ void hlds_row_pf(const IQ *next, __amdgpu_buffer_rsrc
     }
 }
 
+// One antenna row of the ping-pong loop: cur[] holds this row, nxt[] takes
+// the next one (`next`, when PREF).  fp32: the second FFT half lands in cur[]
+// again (dead once the first half has written it to the transpose image), so
+// the row costs no register set beyond cur + nxt + acc and nxt[] is free to
+// take loads from the row's start.  sc16: cur / nxt are the 16 raw dwords,
+// widened here.  The next row's 16 loads are issued in pieces -- PP_A before
+// the first FFT half, PP_B between the halves, PP_C behind the second half,
+// the rest behind the Hc exchange: all 16 at the row's start (in flight for
+// the whole row) measured no faster than the parent, whose 16 sit between
+// the halves; what pays is that a wave never issues more than a few loads
+// at once.  The thread's 16 B of the Hc row are a buffer
+// load -- hc: the frame's estimates, hoff: the byte offset of (row, this
+// wave's 1 KiB), in SGPRs; the lane's offset is formed here, so that no
+// per-thread 64-bit pointer stays live across the loop -- issued in front of
+// the row's loads: the wait for it before the exchange leaves them in flight.
+// The scheduler barriers pin each piece to its place and keep the second FFT
+// half in front of the exchange (left free in the sc16 loop, the scheduler
+// moved it between the two barriers and the allocator spilled accumulators).
+constexpr int PP_A = 4, PP_B = 8, PP_C = 4;
+template <bool PREF, class IQ>
+__device__ __forceinline__ void hlds_row_pp(const IQ *next, __amdgpu_buffer_rsrc_t hc, int hoff, int t,
+                                            row_reg_t<IQ> (&cur)[16], row_reg_t<IQ> (&nxt)[16],
+                                            float2 *T, const float2 *tw1, const float2 *tw2,
+                                            const float4 *lo, const float4 *hi, float4 *mine,
+                                            float2 (&acc)[16]) {
+    using namespace hlds;
+    static_assert(PP_A >= 0 && PP_B >= 0 && PP_C >= 0 && PP_A + PP_B + PP_C <= 16, "the row's 16 loads");
+    const float4 hreg = __builtin_bit_cast(float4, (v4i_t)__builtin_amdgcn_raw_buffer_load_b128(hc, t * 16, hoff, 0));
+    if (PREF) row_load_part<0, PP_A>(next, t, nxt);
+    __builtin_amdgcn_sched_barrier(0);
+    auto rest = [&](float2 (&x)[16]) {
+        fft_a(x, t, T, tw1);
+        __builtin_amdgcn_sched_barrier(0);
+        if (PREF) row_load_part<PP_A, PP_A + PP_B>(next, t, nxt);
+        __builtin_amdgcn_sched_barrier(0);
+        fft_b(t, T, tw2, x);
+        __builtin_amdgcn_sched_barrier(0);
+        if (PREF) row_load_part<PP_A + PP_B, PP_A + PP_B + PP_C>(next, t, nxt);
+        __builtin_amdgcn_sched_barrier(0);
+        lds_barrier();  // every wave is done with the previous Hc row
+        *mine = hreg;
+        lds_barrier();
+        if (PREF) row_load_part<PP_A + PP_B + PP_C, 16>(next, t, nxt);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const float4 v = i < 4 ? lo[i * 64] : hi[(i - 4) * TS];  // 2 images = TS float4s
+            mac(acc[2 * i], x[2 * i], v.x, v.y);
+            mac(acc[2 * i + 1], x[2 * i + 1], v.z, v.w);
+        }
+    };
+    if constexpr (is_sc16<IQ>) {
+        float2 x[16];
+        widen_row(cur, x);
+        rest(x);
+    } else {
+        rest(cur);
+    }
+}
+
 // Antenna-row loop.  SHARED: the workgroup's 8 symbols share one frame and
-// the Hc row goes through LDS, the next row's IQ is loaded into a[] as soon
-// as the first FFT half has written a[] to the transpose image (in flight
-// during the second half, the Hc exchange and the MAC; no extra registers).
+// the Hc row goes through LDS; the rows alternate between two register
+// buffers (hlds_row_pp; the loop is unrolled by two, so no prefetched
+// register is ever moved), the next row's loads spread over the current row.
 // Otherwise (a workgroup straddling a frame boundary) each wave loads its
 // own Hc row from L2.  sc16 rows (IQ = sc16) go through the transform and
 // the MAC as raw integers (|sums| <= 2^15 * 1024 * R: exact headroom in f32);
@@ -208,7 +269,14 @@ template <bool R0, class IQ>
 __device__ __forceinline__ void row0(const IQ *sym, int t, const float2 *T, row_reg_t<IQ> (&a)[16]) {
     if constexpr (R0) {
         static_assert(!is_sc16<IQ>, "sc16 rows are only 4-byte aligned: no 16-B row-0 DMA");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's DMA (the compiler does not count asm loads)
+        // this wave's DMA (the compiler does not count asm loads).  The builtin,
+        // not an asm string: the compiler's own counter bookkeeping then knows
+        // that nothing is outstanding here -- a load it still held pending
+        // from a path in front of the rows (the fallback estimate's pilots)
+        // otherwise becomes a vmcnt(1) at the head of the unrolled row loop,
+        // in front of the next row's loads
+        __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0) alone (expcnt 7, lgkmcnt 15)
+        asm volatile("" ::: "memory");
 #pragma unroll
         for (int m = 0; m < 16; ++m) a[m] = T[t + 64 * m];
     } else {
@@ -236,7 +304,6 @@ __device__ __forceinline__ void hlds_rows(const IQ *sym, int Cp, int R, const fl
     if constexpr (SHARED) {
         row_reg_t<IQ> a[16];
         const int tl = lane_here();  // the caller's t need not stay live up to here
-        row0<R0>(sym, tl, T, a);
         const float4 *lo = hfree + tl;
         const float4 *hi = hslot(T0, hfree, 256 + tl);
         float4 *mine = hslot(T0, hfree, threadIdx.x);
@@ -244,12 +311,40 @@ __device__ __forceinline__ void hlds_rows(const IQ *sym, int Cp, int R, const fl
         const __amdgpu_buffer_rsrc_t hc =
             __builtin_amdgcn_make_buffer_rsrc(const_cast<float4 *>(Hf), (short)0, R * (C * 8), 0x00020000);
         const int hw = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) * 1024;
-        // the last row is peeled so that the prefetch is unconditional: the
-        // wait for the Hc word before the exchange is then vmcnt(16), not 0
-        for (int r = 0; r + 1 < R; ++r)
-            hlds_row_pf<true>(sym + (long long)(r + 1) * Cp, hc, r * (C * 8) + hw, lane_here(), a, T, tw1, tw2, lo,
-                              hi, mine, acc);
-        hlds_row_pf<false>(sym, hc, (R - 1) * (C * 8) + hw, lane_here(), a, T, tw1, tw2, lo, hi, mine, acc);
+        if constexpr (is_sc16<IQ>) {
+            // sc16 keeps one row buffer and the prefetch behind the first FFT
+            // half: with the ping-pong rows its R = 16 x 100-frame batch ran
+            // 6 % slower.  The last row is peeled so that the
+            // prefetch is unconditional: the wait for the Hc word before the
+            // exchange is then vmcnt(16), not 0
+            row0<R0>(sym, tl, T, a);
+            for (int r = 0; r + 1 < R; ++r)
+                hlds_row_pf<true>(sym + (long long)(r + 1) * Cp, hc, r * (C * 8) + hw, lane_here(), a, T, tw1, tw2,
+                                  lo, hi, mine, acc);
+            hlds_row_pf<false>(sym, hc, (R - 1) * (C * 8) + hw, lane_here(), a, T, tw1, tw2, lo, hi, mine, acc);
+        } else {
+            row_reg_t<IQ> b[16];
+            // rows in pairs, a -> b -> a, while two more rows follow; then the
+            // last row (R odd) or the last two (R even), the final one without a
+            // prefetch
+            auto row = [&](auto pref, int r, row_reg_t<IQ>(&cur)[16], row_reg_t<IQ>(&nxt)[16]) {
+                hlds_row_pp<decltype(pref)::value>(sym + (long long)(r + 1) * Cp, hc, r * (C * 8) + hw, lane_here(), cur,
+                                                   nxt, T, tw1, tw2, lo, hi, mine, acc);
+            };
+            int r = 0;
+            if ((R & 1) == 0) {
+                row0<R0>(sym, tl, T, b);
+                row(std::true_type{}, 0, b, a);
+                r = 1;
+            } else {
+                row0<R0>(sym, tl, T, a);
+            }
+            for (; r + 2 < R; r += 2) {
+                row(std::true_type{}, r, a, b);
+                row(std::true_type{}, r + 1, b, a);
+            }
+            row(std::false_type{}, r, a, b);
+        }
     } else {
         for (int r = 0; r < R; ++r) {
             float2 a[16], x[16], h[16];

@@ -125,6 +125,20 @@ __device__ __forceinline__ void row_load(const sc16 *__restrict__ src, int t, un
 #pragma unroll
     for (int m = 0; m < 16; ++m) a[m] = NT ? __builtin_nontemporal_load(p + 64 * m) : p[64 * m];
 }
+// Loads M0 .. M1-1 of a row's 16 (non-temporal): a row prefetched in pieces,
+// issued at several points of the previous row (frame_td.hip, hlds_row_pp).
+template <int M0, int M1>
+__device__ __forceinline__ void row_load_part(const float2 *__restrict__ src, int t, float2 (&a)[16]) {
+    const unsigned long long *p = reinterpret_cast<const unsigned long long *>(src) + t;
+#pragma unroll
+    for (int m = M0; m < M1; ++m) a[m] = __builtin_bit_cast(float2, __builtin_nontemporal_load(p + 64 * m));
+}
+template <int M0, int M1>
+__device__ __forceinline__ void row_load_part(const sc16 *__restrict__ src, int t, unsigned (&a)[16]) {
+    const unsigned *p = reinterpret_cast<const unsigned *>(src) + t;
+#pragma unroll
+    for (int m = M0; m < M1; ++m) a[m] = __builtin_nontemporal_load(p + 64 * m);
+}
 __device__ __forceinline__ float2 widen(unsigned v) {
     return float2{(float)(short)(v & 0xffffu), (float)((int)v >> 16)};
 }
