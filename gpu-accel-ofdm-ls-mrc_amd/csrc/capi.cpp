@@ -635,6 +635,105 @@ int ofdm_frame_demod_sc16(const ofdm_sc16 *d_iq, long long nframes, int S, int R
                      "mrc_td1024_sc16");
 }
 
+// Carrier frequency offset: the checks every *_cfo receiver entry makes after
+// check_frame_args, before any HIP call.
+static int check_cfo(const char *fn, long long nframes, const float *d_eps, int C) {
+    if (nframes > 0 && !d_eps) return fail(OFDM_E_ARG, "%s: null d_eps", fn);
+    if (C != 1024)
+        return fail(OFDM_E_UNSUPPORTED, "%s: C=%d (the derotating receiver covers C = 1024; derotate with "
+                                        "ofdm_frame_cfo_derotate and call the fp32 entry)", fn, C);
+    return OFDM_OK;
+}
+
+int ofdm_frame_cfo_estimate(const ofdm_cf32 *d_iq, long long nframes, int S, int R, int C, int cp_len, int cp_skip,
+                            ofdm_cf32 *d_gamma, float *d_eps, ofdm_stream_t stream) {
+    static const char *fn = "ofdm_frame_cfo_estimate";
+    int rc = check_frame_args(d_iq, nframes, S, R, C, cp_len, d_eps, fn);
+    if (rc) return rc;
+    if (cp_len < 1) return fail(OFDM_E_ARG, "%s: cp_len=%d, the estimator needs a cyclic prefix", fn, cp_len);
+    if (cp_skip < 0 || cp_skip >= cp_len) return fail(OFDM_E_ARG, "%s: cp_skip=%d out of [0, cp_len)", fn, cp_skip);
+    if (nframes == 0) return OFDM_OK;
+    return hip_check(ofdm::launch_cfo_estimate(F2(d_iq), nframes, S, R, C, cp_len, cp_skip, F2(d_gamma), d_eps,
+                                               hs(stream)),
+                     "cfo_estimate");
+}
+
+int ofdm_frame_cfo_derotate(const ofdm_cf32 *d_in, ofdm_cf32 *d_out, long long nframes, int S, int R, int C,
+                            int cp_len, const float *d_eps, ofdm_stream_t stream) {
+    static const char *fn = "ofdm_frame_cfo_derotate";
+    int rc = check_frame_args(d_in, nframes, S, R, C, cp_len, d_out, fn);
+    if (rc) return rc;
+    if (nframes > 0 && !d_eps) return fail(OFDM_E_ARG, "%s: null d_eps", fn);
+    if (!aligned(d_out, 16)) return fail(OFDM_E_ARG, "%s: d_out must be 16-byte aligned", fn);
+    if (nframes == 0) return OFDM_OK;
+    const uintptr_t a = reinterpret_cast<uintptr_t>(d_in), b = reinterpret_cast<uintptr_t>(d_out);
+    const uintptr_t bytes = (uintptr_t)nframes * S * R * (C + cp_len) * sizeof(ofdm_cf32);
+    if (a != b && a < b + bytes && b < a + bytes)
+        return fail(OFDM_E_ARG, "%s: d_out overlaps d_in (in place, d_out == d_in, or disjoint)", fn);
+    return hip_check(ofdm::launch_cfo_derotate(F2(d_in), F2(d_out), nframes, S, R, C, cp_len, d_eps, hs(stream)),
+                     "cfo_derotate");
+}
+
+int ofdm_frame_estimate_cfo(const ofdm_cf32 *d_iq, long long nframes, int S, int R, int C, int prefix,
+                            const ofdm_cf32 *d_X, void *d_ws, size_t ws_bytes_, const float *d_eps,
+                            ofdm_stream_t stream) {
+    static const char *fn = "ofdm_frame_estimate_cfo";
+    int rc = check_frame_args(d_iq, nframes, S, R, C, prefix, d_ws, fn);
+    if (rc) return rc;
+    if ((rc = check_cfo(fn, nframes, d_eps, C))) return rc;
+    if (!d_X) return fail(OFDM_E_ARG, "%s: null pilots", fn);
+    if (nframes == 0) return OFDM_OK;
+    Workspace w;
+    if ((rc = carve(d_ws, ws_bytes_, nframes, S, R, C, false, w))) return rc;
+    ws_forget(d_ws);
+    rc = hip_check(ofdm::launch_ls_td1024_cfo(F2(d_iq), nframes, S, R, prefix, d_eps, F2(d_X), w.Hc, w.P, hs(stream)),
+                   "ls_td1024_cfo");
+    if (rc == OFDM_OK) ws_record(d_ws, ws_bytes_, nframes, S, R, C, true, false);
+    return rc;
+}
+
+int ofdm_frame_combine_cfo(const ofdm_cf32 *d_iq, long long nframes, int S, int R, int C, int prefix, void *d_ws,
+                           size_t ws_bytes_, ofdm_cf32 *d_out, const float *d_eps, ofdm_stream_t stream) {
+    static const char *fn = "ofdm_frame_combine_cfo";
+    if (int st = take_status(fn)) return st;
+    int rc = check_frame_args(d_iq, nframes, S, R, C, prefix, d_out, fn);
+    if (rc) return rc;
+    if ((rc = check_cfo(fn, nframes, d_eps, C))) return rc;
+    if (nframes == 0) return OFDM_OK;
+    WsTag tag;
+    if ((rc = ws_check(d_ws, ws_bytes_, nframes, S, R, C, true, fn, &tag))) return rc;
+    if (!tag.lane_order)
+        return fail(OFDM_E_ARG, "%s: the workspace holds a frequency-domain estimate (use ofdm_frame_combine_freq)", fn);
+    Workspace w;
+    if ((rc = carve(d_ws, ws_bytes_, nframes, S, R, C, false, w))) return rc;
+    return hip_check(ofdm::launch_mrc_td1024_cfo(F2(d_iq), nframes, S, R, prefix, d_eps, w.Hc, w.P, F2(d_out),
+                                                 hs(stream)),
+                     "mrc_td1024_cfo");
+}
+
+int ofdm_frame_demod_cfo(const ofdm_cf32 *d_iq, long long nframes, int S, int R, int C, int prefix,
+                         const ofdm_cf32 *d_X, void *d_ws, size_t ws_bytes_, ofdm_cf32 *d_out, const float *d_eps,
+                         ofdm_stream_t stream) {
+    static const char *fn = "ofdm_frame_demod_cfo";
+    if (int st = take_status(fn)) return st;
+    int rc = check_frame_args(d_iq, nframes, S, R, C, prefix, d_out, fn);
+    if (rc) return rc;
+    if ((rc = check_cfo(fn, nframes, d_eps, C))) return rc;
+    if (!d_X) return fail(OFDM_E_ARG, "%s: null pilots", fn);
+    if (nframes == 0) return OFDM_OK;
+    Workspace w;
+    if ((rc = carve(d_ws, ws_bytes_, nframes, S, R, C, false, w))) return rc;
+    hipStream_t s = hs(stream);
+    ws_forget(d_ws);
+    rc = hip_check(ofdm::launch_ls_td1024_cfo(F2(d_iq), nframes, S, R, prefix, d_eps, F2(d_X), w.Hc, w.P, s),
+                   "ls_td1024_cfo");
+    if (rc) return rc;
+    // the estimate is in the workspace once the LS launch is enqueued
+    ws_record(d_ws, ws_bytes_, nframes, S, R, C, true, false);
+    return hip_check(ofdm::launch_mrc_td1024_cfo(F2(d_iq), nframes, S, R, prefix, d_eps, w.Hc, w.P, F2(d_out), s),
+                     "mrc_td1024_cfo");
+}
+
 int ofdm_frame_estimate_freq(const ofdm_cf32 *d_Y, long long nframes, int S, int R, int C,
                              const ofdm_cf32 *d_X, void *d_ws, size_t ws_bytes_, ofdm_stream_t stream) {
     int rc = check_frame_args(d_Y, nframes, S, R, C, 0, d_ws, "ofdm_frame_estimate_freq");

@@ -51,6 +51,93 @@ namespace td1024 {
 // `scale` (ignored for float2), so Hc and P are in the units of x = i16 * scale.
 constexpr int LS_WAVES = 4;
 
+// ---------------------------------------------------------------------------
+// Carrier frequency offset (cfo.hip states the convention): the _cfo kernels
+// transform x'[n] = y[n] e^{-2 pi i eps (m0 + n) / C}, m0 = s (C + prefix) +
+// prefix the frame-sample index of the symbol's first FFT sample.  Lane t holds
+// n = t + 64 m, so the rotation of a row splits three ways:
+//   e^{-2 pi i eps m0 / C}    one factor per symbol: commutes with the FFT
+//                             and the antenna sum, applied once per output
+//                             (the MRC epilogue; the LS multiplies h by its
+//                             conjugate).  m0 reaches tens of turns: reduced
+//                             modulo one turn in float64.
+//   e^{-2 pi i eps 64 m / C}  15 wave-uniform constants (Rot::cr / ci,
+//                             SGPRs), applied to the row in front of the
+//                             16-point transform over m.
+//   e^{-2 pi i eps t / C}     one factor per lane: commutes with that
+//                             transform.  Where every wave of the workgroup
+//                             has the same eps (the LS; an MRC workgroup inside
+//                             one frame) it is folded into the workgroup's copy
+//                             of the first twiddle table, k2 = 0 apart;
+//                             otherwise (a straddling MRC workgroup) each
+//                             twiddle is multiplied by it from two registers.
+// A non-finite eps acts as 0.
+// ---------------------------------------------------------------------------
+struct Rot {
+    float2 l;               // e^{-2 pi i eps t / C} of this lane
+    float cr[15], ci[15];   // e^{-2 pi i eps 64 m / C}, m = 1..15 (wave-uniform)
+};
+
+__device__ __forceinline__ float cfo_eps(const float *eps, long long f) {
+    const float e = eps[f];
+    return (__builtin_bit_cast(unsigned, e) & 0x7f800000u) == 0x7f800000u ? 0.f : e;
+}
+// e^{2 pi i x}, x in turns (range-reduced by sincospi)
+__device__ __forceinline__ float2 cis_turns(float x) {
+    float sn, cs;
+    sincospif(2.f * x, &sn, &cs);
+    return float2{cs, sn};
+}
+__device__ __forceinline__ float uniform_f(float v) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
+}
+// e^{sign 2 pi i eps m0 / C} for a frame-sample index m0 (wave-uniform): the
+// turns reduced to [-0.5, 0.5] in float64 before the f32 sincospi
+__device__ __forceinline__ float2 cfo_symbol_phase(float eps, long long m0, float sign) {
+    const double turns = (double)eps * (double)m0 * (1.0 / C);
+    const float2 p = cis_turns(sign * (float)(turns - __builtin_rint(turns)));
+    return float2{uniform_f(p.x), uniform_f(p.y)};
+}
+// every lane of the wave active; t the lane index
+__device__ __forceinline__ Rot make_rot(float eps, int t) {
+    Rot r;
+    r.l = cis_turns(-eps * (float)t * (1.f / C));
+    const float2 c = cis_turns(-eps * (float)(t & 15) * (64.f / C));  // lane m < 16 holds constant m
+#pragma unroll
+    for (int m = 1; m < 16; ++m) {
+        r.cr[m - 1] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, c.x), m));
+        r.ci[m - 1] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, c.y), m));
+    }
+    return r;
+}
+__device__ __forceinline__ void rot_row(float2 (&a)[16], const Rot &rot) {
+#pragma unroll
+    for (int m = 1; m < 16; ++m) a[m] = cmul(a[m], float2{rot.cr[m - 1], rot.ci[m - 1]});
+}
+// row_fft (wave_fft1024.hpp) of the rotated row; tw's first table carries the
+// lane factor in every entry, k2 = 0 included (k_ls_td1024_cfo folds it in)
+__device__ __forceinline__ void row_fft_rot(float2 (&a)[16], int t, float2 *T, const float2 *tw, const Rot &rot,
+                                            float2 (&x)[16]) {
+    rot_row(a, rot);
+    fft16_fma(a);
+#pragma unroll
+    for (int k2 = 0; k2 < 16; ++k2) a[k2] = cmul(a[k2], tw[t * TW1P + k2]);
+#pragma unroll
+    for (int k2 = 0; k2 < 16; ++k2) T[k2 * TP + t] = a[k2];
+    wave_lds_sync();
+    const int q = t >> 2, qa = t & 3;
+#pragma unroll
+    for (int l = 0; l < 16; ++l) x[l] = T[q * TP + qa + 4 * l];
+    wave_lds_sync();
+    fft16_fma(x);
+    const float2 *tw2 = tw + TW1BUF + qa * TW2P;
+    const float g = quad_g(qa);
+    x[0] = float2{g * x[0].x, g * x[0].y};
+#pragma unroll
+    for (int k = 1; k < 16; ++k) x[k] = cmul(x[k], tw2[k]);
+    quad_dft(x, qa);
+}
+
 template <int NW, class IQ>
 __global__ void __launch_bounds__(64 * NW) k_ls_td1024(const IQ *__restrict__ iq, int S, int R,
                                                        int prefix, const float2 *__restrict__ X,
@@ -113,6 +200,70 @@ __global__ void __launch_bounds__(64 * NW) k_ls_td1024(const IQ *__restrict__ iq
     }
 }
 
+// k_ls_td1024<NW, float2> on x' (eps: one offset per frame): the same body
+// with the rotation in -- a kernel of its own, so that the others' code
+// generation is not touched.
+template <int NW>
+__global__ void __launch_bounds__(64 * NW) k_ls_td1024_cfo(const float2 *__restrict__ iq, int S, int R,
+                                                           int prefix, const float2 *__restrict__ X,
+                                                           float2 *__restrict__ Hc, float *__restrict__ P,
+                                                           int partial, const float *__restrict__ eps) {
+    extern __shared__ __attribute__((aligned(16))) float2 lds[];
+    float2 *tw = lds;
+    const int w = threadIdx.x >> 6;
+    const int t = threadIdx.x & 63;
+    float2 *T = lds + TWBUF + w * TBUF;
+    fill_twiddles(tw);
+    const float e = uniform_f(cfo_eps(eps, blockIdx.x));
+    // the lane factor into the table entries this thread has just written
+    for (int i = threadIdx.x; i < TW1BUF; i += blockDim.x)
+        if (i % TW1P < 16) tw[i] = cmul(tw[i], cis_turns(-e * (float)(i / TW1P) * (1.f / C)));
+    const Rot rot = make_rot(e, t);
+    const float2 p0 = cfo_symbol_phase(e, prefix, 1.f);  // conj(Y' / X) = conj(Y / X) e^{+2 pi i eps prefix / C}
+    __syncthreads();
+
+    const long long f = blockIdx.x;
+    const int Cp = C + prefix;
+    const float2 *pilot = iq + f * (long long)S * R * Cp + prefix;
+    float4 *Hf = reinterpret_cast<float4 *>(Hc + f * (long long)R * C);
+    const int b0 = lane_bin0(t);
+    float2 xp[16];  // rotated pilots of this lane's subcarriers
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        const int b = b0 + 16 * k;
+        xp[k] = b > 0 ? X[b - 1] : float2{1.f, 0.f};
+    }
+    float p[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) p[k] = 0.f;
+    for (int r = w; r < R; r += NW) {
+        float2 a[16], x[16];
+        row_load(pilot + (long long)r * Cp, t, a);
+        row_fft_rot(a, t, T, tw, rot, x);
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            float2 h = cmul(ls_conj(x[k], xp[k]), p0);
+            if (b0 + 16 * k == 0) h = float2{0.f, 0.f};
+            x[k] = h;
+            p[k] = p[k] + (h.x * h.x) + (h.y * h.y);
+        }
+        hc_store(Hf + (long long)r * (C / 2), t, x);
+    }
+    __syncthreads();
+    float *pp = reinterpret_cast<float *>(lds + TWBUF);  // [NW][C], reuses T
+    static_assert(NW * C * sizeof(float) <= NW * TBUF * sizeof(float2), "partials fit the transpose images");
+#pragma unroll
+    for (int k = 0; k < 16; ++k) pp[w * C + b0 + 16 * k] = p[k];
+    __syncthreads();
+    float *Pf = P + f * C;
+    const int nw = R < NW ? R : NW;  // waves that hold rows
+    for (int b = threadIdx.x; b < C; b += blockDim.x) {
+        float sum = pp[b];
+        for (int i = 1; i < nw; ++i) sum = sum + pp[i * C + b];
+        Pf[b] = b == 0 ? (partial ? 0.f : 1.f) : sum;
+    }
+}
+
 // ---------------------------------------------------------------------------
 // MRC with the channel estimates staged in LDS (HLDS): the 8 waves of a
 // workgroup walk the antenna rows in lockstep; each thread prefetches 16 B of
@@ -138,6 +289,21 @@ __device__ __forceinline__ void fft_a(float2 (&a)[16], int t, float2 *T, const f
 }
 __device__ __forceinline__ void fft_b(int t, float2 *T, const float2 *tw2, float2 (&x)[16]) {
     hlds::row_fft_b<0, false, true>(t, T, tw2, x);
+}
+// fft_a of the row rotated by rot.  FOLDED: tw1 is the workgroup's table with
+// the lane factor folded in (k2 = 1..15).
+template <bool FOLDED>
+__device__ __forceinline__ void fft_a_rot(float2 (&a)[16], int t, float2 *T, const float2 *tw1, const Rot &rot) {
+    rot_row(a, rot);
+    fft16_fma(a);
+    a[0] = cmul(a[0], rot.l);
+#pragma unroll
+    for (int k2 = 1; k2 < 16; ++k2) {
+        const float2 w = tw1[(k2 - 1) * 64 + t];
+        a[k2] = cmul(a[k2], FOLDED ? w : cmul(w, rot.l));
+    }
+#pragma unroll
+    for (int k2 = 0; k2 < 16; ++k2) T[hlds::swz(k2, t)] = a[k2];
 }
 // acc += x * v, matrixMultThenSum (cpuLS.hpp:203-204) with the antennas in
 // order, as two chained FMAs per component (64 VALU per row for the 16 bins;
@@ -370,6 +536,90 @@ __device__ __forceinline__ void hlds_rows(const IQ *sym, int Cp, int R, const fl
     }
 }
 
+// The rows of k_mrc_td1024_hlds_cfo: hlds_row_pp / hlds_rows for fp32 rows with
+// the CFO rotation in (fft_a_rot), functions of their own so that the code
+// generation of the kernels without a rotation is not touched.  SHARED takes
+// tw1 with the lane factor folded in.
+template <bool PREF>
+__device__ __forceinline__ void hlds_row_pp_cfo(const float2 *next, __amdgpu_buffer_rsrc_t hc, int hoff, int t,
+                                                float2 (&cur)[16], float2 (&nxt)[16], float2 *T,
+                                                const float2 *tw1, const float2 *tw2, const float4 *lo,
+                                                const float4 *hi, float4 *mine, float2 (&acc)[16],
+                                                const Rot &rot) {
+    using namespace hlds;
+    const float4 hreg = __builtin_bit_cast(float4, (v4i_t)__builtin_amdgcn_raw_buffer_load_b128(hc, t * 16, hoff, 0));
+    if (PREF) row_load_part<0, PP_A>(next, t, nxt);
+    __builtin_amdgcn_sched_barrier(0);
+    fft_a_rot<true>(cur, t, T, tw1, rot);
+    __builtin_amdgcn_sched_barrier(0);
+    if (PREF) row_load_part<PP_A, PP_A + PP_B>(next, t, nxt);
+    __builtin_amdgcn_sched_barrier(0);
+    fft_b(t, T, tw2, cur);
+    __builtin_amdgcn_sched_barrier(0);
+    if (PREF) row_load_part<PP_A + PP_B, PP_A + PP_B + PP_C>(next, t, nxt);
+    __builtin_amdgcn_sched_barrier(0);
+    lds_barrier();  // every wave is done with the previous Hc row
+    *mine = hreg;
+    lds_barrier();
+    if (PREF) row_load_part<PP_A + PP_B + PP_C, 16>(next, t, nxt);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const float4 v = i < 4 ? lo[i * 64] : hi[(i - 4) * TS];  // 2 images = TS float4s
+        mac(acc[2 * i], cur[2 * i], v.x, v.y);
+        mac(acc[2 * i + 1], cur[2 * i + 1], v.z, v.w);
+    }
+}
+template <bool SHARED>
+__device__ __forceinline__ void hlds_rows_cfo(const float2 *sym, int Cp, int R, const float4 *Hf, int t, float2 *T,
+                                              const float2 *tw1, const float2 *tw2, float2 *T0, float4 *hfree,
+                                              float2 (&acc)[16], const Rot &rot) {
+    using namespace hlds;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) acc[k] = float2{0.f, 0.f};
+    if constexpr (SHARED) {
+        float2 a[16], b[16];
+        const int tl = lane_here();
+        const float4 *lo = hfree + tl;
+        const float4 *hi = hslot(T0, hfree, 256 + tl);
+        float4 *mine = hslot(T0, hfree, threadIdx.x);
+        const __amdgpu_buffer_rsrc_t hc =
+            __builtin_amdgcn_make_buffer_rsrc(const_cast<float4 *>(Hf), (short)0, R * (C * 8), 0x00020000);
+        const int hw = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) * 1024;
+        auto row = [&](auto pref, int r, float2(&cur)[16], float2(&nxt)[16]) {
+            hlds_row_pp_cfo<decltype(pref)::value>(sym + (long long)(r + 1) * Cp, hc, r * (C * 8) + hw, lane_here(),
+                                                   cur, nxt, T, tw1, tw2, lo, hi, mine, acc, rot);
+        };
+        int r = 0;
+        if ((R & 1) == 0) {
+            row0<true>(sym, tl, T, b);
+            row(std::true_type{}, 0, b, a);
+            r = 1;
+        } else {
+            row0<true>(sym, tl, T, a);
+        }
+        for (; r + 2 < R; r += 2) {
+            row(std::true_type{}, r, a, b);
+            row(std::true_type{}, r + 1, b, a);
+        }
+        row(std::false_type{}, r, a, b);
+    } else {
+        for (int r = 0; r < R; ++r) {
+            float2 a[16], x[16], h[16];
+            if (r == 0)
+                row0<true>(sym, t, T, a);
+            else
+                row_load<true>(sym + (long long)r * Cp, t, a);
+            fft_a_rot<false>(a, t, T, tw1, rot);
+            fft_b(t, T, tw2, x);
+            __builtin_amdgcn_sched_barrier(0);
+            hc_load(Hf + (long long)r * (C / 2), t, h);
+#pragma unroll
+            for (int k = 0; k < 16; ++k) mac(acc[k], x[k], h[k].x, h[k].y);
+        }
+    }
+}
+
 // Epilogue of one symbol (mode 0: normalise by P): stage the K outputs in
 // this wave's transpose image (free after the last row; its padding tails
 // still hold other waves' Hc words, so index it as [16][TP]) at their final
@@ -475,6 +725,68 @@ k_mrc_td1024_hlds(const IQ *__restrict__ iq, int S, int R, int prefix, const flo
         hlds_epilogue<true>(acc, P, f, q, lane_here(), T, out, mode, scale);
     else
         hlds_epilogue(acc, P, f, q, lane_here(), T, out, mode);
+}
+
+
+// k_mrc_td1024_hlds<true, float2> on x' (eps: one offset per frame) against the
+// estimate of x': the same body with the rotation in -- a kernel of its own,
+// so that the others' code generation is not touched.
+__global__ void __attribute__((amdgpu_flat_work_group_size(512, 512), amdgpu_waves_per_eu(4, 4)))
+k_mrc_td1024_hlds_cfo(const float2 *__restrict__ iq, int S, int R, int prefix, const float2 *__restrict__ Hc,
+                      const float *__restrict__ P, float2 *__restrict__ out, long long nq, long long nblocks,
+                      long long per_xcd, int mode, const float *__restrict__ eps) {
+    constexpr bool R0 = true;  // row 0 by LDS-DMA, as the fp32 kernel
+    using namespace hlds;
+    constexpr int HW = WAVES;
+    extern __shared__ __attribute__((aligned(16))) float2 lds[];
+    float2 *tw1 = lds, *tw2 = lds + TW1S;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), t = threadIdx.x & 63;
+    float2 *T = lds + TW1S + TW2S + w * TS;
+    float2 *T0 = lds + TW1S + TW2S;
+    float4 *hfree = reinterpret_cast<float4 *>(T0 + HW * TS);
+    const long long pb = blockIdx.x;
+    const long long lb = (pb & 7) * per_xcd + (pb >> 3);  // XCD-grouped logical block
+    if (lb >= nblocks) return;
+
+    // every wave takes part in the per-row barriers: tail waves duplicate the
+    // last symbol and do not store
+    const int nsym = S - 1;
+    const long long qw = lb * HW + w;
+    const bool store = qw < nq;
+    const long long q = store ? qw : nq - 1;
+    // the workgroup's Hc rows come from the frame of its first symbol; a
+    // workgroup straddling two frames falls back to per-wave L2 loads
+    const long long f = uniform64(q / nsym);  // wave-uniform: SGPRs across the row loop
+    const long long f0 = (lb * HW) / nsym;
+    const long long fl = ((lb * HW + HW - 1 < nq ? lb * HW + HW - 1 : nq - 1)) / nsym;
+    const int s = 1 + (int)(q % nsym);
+    const int Cp = C + prefix;
+    const float2 *sym = iq + (f * S + s) * (long long)R * Cp + prefix;
+    if constexpr (R0) row0_dma(sym, t, T);
+    fill(tw1, tw2);
+    // this wave's frame: every wave of a workgroup inside one frame has the same
+    // offset, and each thread folds its lane factor into the table entries it
+    // has just written itself (fill: i = threadIdx.x, + 512; i % 64 = t)
+    const float e = uniform_f(cfo_eps(eps, f));
+    const Rot rot = make_rot(e, t);
+    if (f0 == fl) {
+        for (int i = threadIdx.x; i < TW1S; i += blockDim.x) tw1[i] = cmul(tw1[i], rot.l);
+    }
+    __syncthreads();
+
+    float2 acc[16];
+    if (f0 == fl)
+        hlds_rows_cfo<true>(sym, Cp, R, reinterpret_cast<const float4 *>(Hc + f0 * (long long)R * C), t, T, tw1,
+                            tw2, T0, hfree, acc, rot);
+    else
+        hlds_rows_cfo<false>(sym, Cp, R, reinterpret_cast<const float4 *>(Hc + f * (long long)R * C), t, T, tw1,
+                             tw2, T0, hfree, acc, rot);
+    if (!store) return;
+    // the symbol's start phase, once per output
+    const float2 ps = cfo_symbol_phase(e, (long long)s * Cp + prefix, -1.f);
+#pragma unroll
+    for (int k = 0; k < 16; ++k) acc[k] = cmul(acc[k], ps);
+    hlds_epilogue(acc, P, f, q, lane_here(), T, out, mode);
 }
 
 
@@ -728,15 +1040,35 @@ k_demod_td1024(const float2 *__restrict__ iq, int S, int R, int prefix, const fl
 }  // namespace td1024
 
 namespace {
+// eps != null: the CFO kernels (fp32 only; their last argument is eps where
+// the others take the sc16 scale)
 template <class IQ>
 hipError_t ls_td1024(const IQ *iq, long long nframes, int S, int R, int prefix, float scale,
-                     const float2 *X, float2 *Hc, float *P, int partial, hipStream_t s) {
+                     const float2 *X, float2 *Hc, float *P, int partial, hipStream_t s,
+                     const float *eps = nullptr) {
     using namespace td1024;
     if (nframes <= 0) return hipSuccess;
     if (nframes > 0x7fffffffll) return hipErrorInvalidValue;
     // 4-wave workgroups unless they leave the GPU under-filled: fewer than
     // 2 waves per SIMD (2048 waves) with rows left to spread
     int nw = (nframes * LS_WAVES < 2048 && R > LS_WAVES) ? 16 : LS_WAVES;
+    if constexpr (!is_sc16<IQ>) {
+        if (eps) {
+            if (nw == 16) {
+                const size_t lds = (TWBUF + 16 * TBUF) * sizeof(float2);
+                if (hipError_t e = opt_in_lds(reinterpret_cast<const void *>(k_ls_td1024_cfo<16>), (int)lds);
+                    e != hipSuccess)
+                    return e;
+                hipLaunchKernelGGL(k_ls_td1024_cfo<16>, dim3((unsigned)nframes), dim3(64 * 16), lds, s, iq, S, R,
+                                   prefix, X, Hc, P, partial, eps);
+            } else {
+                const size_t lds = (TWBUF + LS_WAVES * TBUF) * sizeof(float2);
+                hipLaunchKernelGGL(k_ls_td1024_cfo<LS_WAVES>, dim3((unsigned)nframes), dim3(64 * LS_WAVES), lds, s,
+                                   iq, S, R, prefix, X, Hc, P, partial, eps);
+            }
+            return hipGetLastError();
+        }
+    }
     auto k16 = k_ls_td1024<16, IQ>;
     auto k4 = k_ls_td1024<LS_WAVES, IQ>;
     auto k8 = k16;  // 8-wave workgroups: A/B build only
@@ -756,7 +1088,8 @@ hipError_t ls_td1024(const IQ *iq, long long nframes, int S, int R, int prefix, 
 
 template <class IQ>
 hipError_t mrc_td1024(const IQ *iq, long long nframes, int S, int R, int prefix, float scale,
-                      const float2 *Hc, const float *P, float2 *out, int mode, hipStream_t s) {
+                      const float2 *Hc, const float *P, float2 *out, int mode, hipStream_t s,
+                      const float *eps = nullptr) {
     using namespace td1024;
     const long long nq = nframes * (S - 1);
     if (nq <= 0) return hipSuccess;
@@ -770,6 +1103,13 @@ hipError_t mrc_td1024(const IQ *iq, long long nframes, int S, int R, int prefix,
     // without scratch (profiles/r6/r6m2_*).
     // sc16 rows are only 4-byte aligned (any cp_len): their row 0 comes by
     // naturally aligned dword loads like every other row, not by 16-B DMA.
+    if constexpr (!is_sc16<IQ>) {
+        if (eps) {
+            hipLaunchKernelGGL(k_mrc_td1024_hlds_cfo, dim3((unsigned)(pxcd * 8)), dim3(64 * hlds::WAVES),
+                               hlds::LDS_BYTES, s, iq, S, R, prefix, Hc, P, out, nq, nb, pxcd, mode, eps);
+            return hipGetLastError();
+        }
+    }
     auto kern = k_mrc_td1024_hlds<!is_sc16<IQ>, IQ>;
     hipLaunchKernelGGL(kern, dim3((unsigned)(pxcd * 8)), dim3(64 * hlds::WAVES), hlds::LDS_BYTES, s, iq, S, R,
                        prefix, Hc, P, out, nq, nb, pxcd, mode, scale);
@@ -793,6 +1133,14 @@ hipError_t launch_mrc_td1024(const float2 *iq, long long nframes, int S, int R, 
 hipError_t launch_mrc_td1024_sc16(const sc16 *iq, long long nframes, int S, int R, int prefix, float scale,
                                   const float2 *Hc, const float *P, float2 *out, int mode, hipStream_t s) {
     return mrc_td1024(iq, nframes, S, R, prefix, scale, Hc, P, out, mode, s);
+}
+hipError_t launch_ls_td1024_cfo(const float2 *iq, long long nframes, int S, int R, int prefix, const float *eps,
+                                const float2 *X, float2 *Hc, float *P, hipStream_t s) {
+    return ls_td1024(iq, nframes, S, R, prefix, 1.f, X, Hc, P, 0, s, eps);
+}
+hipError_t launch_mrc_td1024_cfo(const float2 *iq, long long nframes, int S, int R, int prefix, const float *eps,
+                                 const float2 *Hc, const float *P, float2 *out, hipStream_t s) {
+    return mrc_td1024(iq, nframes, S, R, prefix, 1.f, Hc, P, out, 0, s, eps);
 }
 
 // One-launch LS + MRC (ofdm_frame_demod, mode 0).  flags: nframes 64-bit

@@ -151,6 +151,22 @@ hipError_t launch_mrc_td1024_sc16(const sc16 *iq, long long nframes, int S, int 
 // and out 16-B aligned.
 hipError_t launch_iq_sc16_to_cf32(const sc16 *in, long long n, float scale, float2 *out, hipStream_t s);
 
+// Carrier frequency offset (cfo.hip states the convention; eps: one offset per
+// frame, in subcarrier spacings).  cfo_estimate: gamma[f] (may be null) and
+// eps[f] = arg(gamma[f]) / 2 pi from the cyclic prefixes of frame f, samples
+// cp_skip .. cp-1 of every row; any C.  cfo_derotate: out = in e^{-2 pi i eps m
+// / C} over whole rows, out == in or disjoint.  The _cfo launchers: the
+// two-launch C = 1024 receiver (frame_td.hip) on the derotated frames, full
+// demod (mode 0, no antenna split).
+hipError_t launch_cfo_estimate(const float2 *iq, long long nframes, int S, int R, int C, int cp, int cp_skip,
+                               float2 *gamma, float *eps, hipStream_t s);
+hipError_t launch_cfo_derotate(const float2 *in, float2 *out, long long nframes, int S, int R, int C, int cp,
+                               const float *eps, hipStream_t s);
+hipError_t launch_ls_td1024_cfo(const float2 *iq, long long nframes, int S, int R, int prefix, const float *eps,
+                                const float2 *X, float2 *Hc, float *P, hipStream_t s);
+hipError_t launch_mrc_td1024_cfo(const float2 *iq, long long nframes, int S, int R, int prefix, const float *eps,
+                                 const float2 *Hc, const float *P, float2 *out, hipStream_t s);
+
 // Stage-wise operations of the reference's per-stage gpuLS methods (stages.hip).
 // fused time-domain receiver, C = 2048 (frame_td2048.hip); same contracts
 hipError_t launch_ls_td2048(const float2 *iq, long long nframes, int S, int R, int prefix,

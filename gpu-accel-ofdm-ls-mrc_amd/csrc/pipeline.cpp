@@ -30,6 +30,7 @@ struct ofdm_pipeline {
         void *iq = nullptr;          // chunk frames of ofdm_cf32, or of ofdm_sc16 (sc16 pipelines)
         ofdm_cf32 *f32 = nullptr;    // sc16 pipelines at C != 1024: the converted chunk
         ofdm_cf32 *out = nullptr;
+        float *eps = nullptr;        // ofdm_pipeline_set_cfo: the chunk's per-frame offsets
         void *ws = nullptr;
         hipEvent_t in_done = nullptr, comp_done = nullptr, out_done = nullptr;
         bool used = false;       // has been submitted at least once
@@ -39,6 +40,8 @@ struct ofdm_pipeline {
     bool sc16 = false;  // the slots hold ofdm_sc16 samples, x = i16 * scale
     float scale = 1.f;
     int taps_post = 0, taps_pre = 0;  // ofdm_pipeline_set_denoise; taps_post == 0: off
+    bool cfo = false;                 // ofdm_pipeline_set_cfo
+    int cp_skip = 0;
     long long chunk = 0;
     size_t ws_bytes = 0, frame_in = 0, frame_out = 0;  // elements
     ofdm_cf32 *X = nullptr;
@@ -90,6 +93,7 @@ void release(ofdm_pipeline *p) {
         if (s.iq) (void)hipFree(s.iq);
         if (s.f32) (void)hipFree(s.f32);
         if (s.out) (void)hipFree(s.out);
+        if (s.eps) (void)hipFree(s.eps);
         if (s.ws) {
             (void)ofdm_workspace_release(s.ws);  // its registry entry must not outlive the memory
             (void)hipFree(s.ws);
@@ -258,7 +262,41 @@ int ofdm_pipeline_submit(ofdm_pipeline *p, long long nframes, ofdm_cf32 *out) {
     rel.enqueued = true;
     PL_TRY(hipStreamWaitEvent(p->s_comp, s.in_done, 0), fn, "hipStreamWaitEvent");
     if (s.used) PL_TRY(hipStreamWaitEvent(p->s_comp, s.out_done, 0), fn, "hipStreamWaitEvent");
-    if (nframes > 0 && p->taps_post > 0) {
+    if (nframes > 0 && p->cfo) {
+        // the chunk's offsets from its cyclic prefixes, then the derotating
+        // receiver (C = 1024) or the slot derotated in place and the fp32 forms
+        // (the slot, or the converted chunk of an sc16 pipeline, is the
+        // pipeline's own memory)
+        ofdm_cf32 *iq = s.f32 ? s.f32 : static_cast<ofdm_cf32 *>(s.iq);
+        const bool fused = p->C == 1024;
+        int rc = OFDM_OK;
+        if (s.f32)
+            rc = ofdm_iq_convert_sc16(static_cast<const ofdm_sc16 *>(s.iq), (long long)(nframes * p->frame_in), p->scale,
+                                      s.f32, p->s_comp);
+        if (rc == OFDM_OK)
+            rc = ofdm_frame_cfo_estimate(iq, nframes, p->S, p->R, p->C, p->cp, p->cp_skip, nullptr, s.eps, p->s_comp);
+        if (rc == OFDM_OK && !fused)
+            rc = ofdm_frame_cfo_derotate(iq, iq, nframes, p->S, p->R, p->C, p->cp, s.eps, p->s_comp);
+        if (rc == OFDM_OK && p->taps_post > 0) {
+            rc = fused ? ofdm_frame_estimate_cfo(iq, nframes, p->S, p->R, p->C, p->cp, p->X, s.ws, p->ws_bytes, s.eps,
+                                                 p->s_comp)
+                       : ofdm_frame_estimate(iq, nframes, p->S, p->R, p->C, p->cp, p->X, s.ws, p->ws_bytes, p->s_comp);
+            if (rc == OFDM_OK)
+                rc = ofdm_frame_estimate_denoise(s.ws, p->ws_bytes, nframes, p->S, p->R, p->C, p->taps_post,
+                                                 p->taps_pre, p->s_comp);
+            if (rc == OFDM_OK)
+                rc = fused ? ofdm_frame_combine_cfo(iq, nframes, p->S, p->R, p->C, p->cp, s.ws, p->ws_bytes, s.out,
+                                                    s.eps, p->s_comp)
+                           : ofdm_frame_combine(iq, nframes, p->S, p->R, p->C, p->cp, s.ws, p->ws_bytes, s.out,
+                                                p->s_comp);
+        } else if (rc == OFDM_OK) {
+            rc = fused ? ofdm_frame_demod_cfo(iq, nframes, p->S, p->R, p->C, p->cp, p->X, s.ws, p->ws_bytes, s.out,
+                                              s.eps, p->s_comp)
+                       : ofdm_frame_demod(iq, nframes, p->S, p->R, p->C, p->cp, p->X, s.ws, p->ws_bytes, s.out,
+                                          p->s_comp);
+        }
+        if (rc) return rc;
+    } else if (nframes > 0 && p->taps_post > 0) {
         // estimate -> denoise -> combine (the one-launch demod cannot take the denoising in)
         const bool sc = p->sc16 && !s.f32;
         const ofdm_cf32 *iq = static_cast<const ofdm_cf32 *>(s.f32 ? s.f32 : s.iq);
@@ -316,6 +354,26 @@ int ofdm_pipeline_set_denoise(ofdm_pipeline *p, int taps_post, int taps_pre) {
     if (taps_post > p->C - taps_pre) return err(OFDM_E_ARG, fn, "taps_post + taps_pre exceeds C");
     p->taps_post = taps_post;
     p->taps_pre = taps_pre;
+    return OFDM_OK;
+}
+
+int ofdm_pipeline_set_cfo(ofdm_pipeline *p, int on, int cp_skip) {
+    static const char *fn = "ofdm_pipeline_set_cfo";
+    if (!p) return err(OFDM_E_ARG, fn, "null pipeline");
+    if (!on) {
+        p->cfo = false;
+        return OFDM_OK;
+    }
+    if (p->cp == 0) return err(OFDM_E_ARG, fn, "cp_len == 0: the estimator needs a cyclic prefix");
+    if (cp_skip < 0 || cp_skip >= p->cp) return err(OFDM_E_ARG, fn, "cp_skip out of [0, cp_len)");
+    if (p->sc16 && p->C == 1024)
+        return err(OFDM_E_UNSUPPORTED, fn, "an sc16 pipeline at C = 1024 has no derotating receiver");
+    DeviceGuard dg(p->device);
+    PL_TRY(dg.e, fn, "hipSetDevice");
+    for (auto &s : p->slots)
+        if (!s.eps) PL_TRY(hipMalloc(&s.eps, (size_t)p->chunk * sizeof(float)), fn, "hipMalloc(eps slot)");
+    p->cfo = true;
+    p->cp_skip = cp_skip;
     return OFDM_OK;
 }
 

@@ -80,6 +80,12 @@ _SIGS = {
     "ofdm_pipeline_create_sc16": (_I, [_I, _I, _I, _I, _c.c_float, _P, _I, _I, _c.POINTER(_P)]),
     "ofdm_pipeline_acquire_sc16": (_I, [_P, _c.POINTER(_P), _c.POINTER(_P)]),
     "ofdm_pipeline_demod_sc16": (_I, [_P, _P, _LL, _P]),
+    "ofdm_frame_cfo_estimate": (_I, [_P, _LL, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "ofdm_frame_cfo_derotate": (_I, [_P, _P, _LL, _I, _I, _I, _I, _P, _P]),
+    "ofdm_frame_estimate_cfo": (_I, [_P, _LL, _I, _I, _I, _I, _P, _P, _c.c_size_t, _P, _P]),
+    "ofdm_frame_combine_cfo": (_I, [_P, _LL, _I, _I, _I, _I, _P, _c.c_size_t, _P, _P, _P]),
+    "ofdm_frame_demod_cfo": (_I, [_P, _LL, _I, _I, _I, _I, _P, _P, _c.c_size_t, _P, _P, _P]),
+    "ofdm_pipeline_set_cfo": (_I, [_P, _I, _I]),
     "ofdm_host_register": (_I, [_P, _c.c_size_t]),
     "ofdm_host_unregister": (_I, [_P]),
     "ofdm_pn_correlate": (_I, [_P, _I, _LL, _P, _I, _c.c_float, _P, _P, _P]),
@@ -438,6 +444,74 @@ def frame_combine_sc16(iq, prefix, ws, out, scale=SC16_SCALE, stream=None):
     F, S, R, Cp, _ = iq.shape
     _check(lib().ofdm_frame_combine_sc16(p, F, S, R, Cp - prefix, prefix, scale, _dptr(ws), ws.numel(), _dptr(out),
                                          _stream(stream)), "ofdm_frame_combine_sc16")
+    return out
+
+
+def _eps(eps, F, name="eps"):
+    """The device pointer of the per-frame offsets, float32 (F,)."""
+    import torch
+    if not isinstance(eps, torch.Tensor) or eps.dtype != torch.float32 or tuple(eps.shape) != (F,):
+        raise OfdmError(f"{name} must be a torch.float32 tensor of shape ({F},)")
+    return _dptr(eps, name) if F else None
+
+
+def frame_cfo_estimate(iq, prefix, cp_skip=0, eps=None, gamma=None, stream=None):
+    """Carrier frequency offset of every frame from its cyclic prefixes: iq
+    (F, S, R, C+prefix) -> eps (F,) float32 in subcarrier spacings, in
+    (-0.5, 0.5].  cp_skip: prefix samples left out at each symbol's head.
+    gamma (F,) complex64, when given, receives the prefix correlations."""
+    import torch
+    F, S, R, Cp = iq.shape
+    if eps is None:
+        eps = torch.empty(F, dtype=torch.float32, device=iq.device)
+    _check(lib().ofdm_frame_cfo_estimate(_dptr(iq, "iq") if F else None, F, S, R, Cp - prefix, prefix, cp_skip,
+                                         None if gamma is None else _dptr(gamma, "gamma"), _eps(eps, F),
+                                         _stream(stream)), "ofdm_frame_cfo_estimate")
+    return eps
+
+
+def frame_cfo_derotate(iq, prefix, eps, out=None, stream=None):
+    """x' = iq e^{-2 pi i eps_f m / C} over whole frames (m: the sample's index
+    in its frame and antenna row, prefix included); out=iq works in place.
+    The route to the fp32 entries for every C but 1024 (frame_demod_cfo)."""
+    F, S, R, Cp = iq.shape
+    if out is None:
+        out = c64(tuple(iq.shape), iq.device)
+    _check(lib().ofdm_frame_cfo_derotate(_dptr(iq, "iq") if F else None, _dptr(out, "out") if F else None, F, S, R,
+                                         Cp - prefix, prefix, _eps(eps, F), _stream(stream)),
+           "ofdm_frame_cfo_derotate")
+    return out
+
+
+def frame_demod_cfo(iq, X, prefix, eps, ws=None, out=None, stream=None):
+    """frame_demod (two launches) on the frames derotated by eps (F,) float32,
+    the rotation applied as each row is loaded.  C = 1024 (else
+    frame_cfo_derotate, then frame_demod)."""
+    F, S, R, Cp = iq.shape
+    C = Cp - prefix
+    if ws is None:
+        ws = workspace(F, S, R, C, iq.device)
+    if out is None:
+        out = c64((F, S - 1, C - 1), iq.device)
+    _check(lib().ofdm_frame_demod_cfo(_dptr(iq), F, S, R, C, prefix, _dptr(X), _dptr(ws), ws.numel(), _dptr(out),
+                                      _eps(eps, F), _stream(stream)), "ofdm_frame_demod_cfo")
+    return out
+
+
+def frame_estimate_cfo(iq, X, prefix, ws, eps, stream=None):
+    """LS stage of frame_demod_cfo: the estimate of the derotated frames, for
+    every consumer of a workspace estimate."""
+    F, S, R, Cp = iq.shape
+    _check(lib().ofdm_frame_estimate_cfo(_dptr(iq), F, S, R, Cp - prefix, prefix, _dptr(X), _dptr(ws), ws.numel(),
+                                         _eps(eps, F), _stream(stream)), "ofdm_frame_estimate_cfo")
+    return ws
+
+
+def frame_combine_cfo(iq, prefix, ws, out, eps, stream=None):
+    """MRC stage of frame_demod_cfo against the estimate in ws."""
+    F, S, R, Cp = iq.shape
+    _check(lib().ofdm_frame_combine_cfo(_dptr(iq), F, S, R, Cp - prefix, prefix, _dptr(ws), ws.numel(), _dptr(out),
+                                        _eps(eps, F), _stream(stream)), "ofdm_frame_combine_cfo")
     return out
 
 
@@ -803,6 +877,13 @@ class Pipeline:
         """Later submits run estimate -> frame_estimate_denoise -> combine;
         taps_post = 0 turns it off again (the default)."""
         _check(lib().ofdm_pipeline_set_denoise(self._h, taps_post, taps_pre), "ofdm_pipeline_set_denoise")
+
+    def set_cfo(self, on=True, cp_skip=0):
+        """Later submits estimate each frame's carrier frequency offset from
+        its cyclic prefixes (frame_cfo_estimate) and remove it: the derotating
+        receiver at C = 1024, frame_cfo_derotate on the slot at any other C.
+        on=False turns it off again (the default)."""
+        _check(lib().ofdm_pipeline_set_cfo(self._h, int(bool(on)), cp_skip), "ofdm_pipeline_set_cfo")
 
     def close(self):
         if getattr(self, "_h", None):

@@ -502,6 +502,78 @@ int ofdm_pipeline_create_sc16(int S, int R, int C, int cp_len, float scale, cons
 int ofdm_pipeline_acquire_sc16(ofdm_pipeline *p, ofdm_sc16 **d_iq, ofdm_stream_t *copy_stream);
 int ofdm_pipeline_demod_sc16(ofdm_pipeline *p, const ofdm_sc16 *iq, long long nframes, ofdm_cf32 *out);
 
+/* ------------------------------------------ carrier frequency offset --- */
+/* The reference's receive driver defaults its clock reference to "internal"
+ * (rx_and_corr.cpp:116): free-running oscillators.  A frame is one pilot and
+ * then data symbols combined against that one estimate, so a carrier
+ * frequency offset (CFO) of eps subcarrier spacings turns every later symbol
+ * by a further 2 pi eps (C + cp_len) / C.  These entries estimate eps per
+ * frame from the cyclic prefix and remove it.
+ *
+ * Conventions: eps is in subcarrier spacings, cycles per C samples.  A
+ * received frame is y[m] = x[m] e^{+2 pi i eps m / C}, m = s (C + cp_len) + i
+ * counting the frame's samples per antenna row from the first prefix sample
+ * of symbol 0, i in [0, C + cp_len).  Every frame has its own eps: d_eps is
+ * float[nframes] on the device.  Every *_cfo entry is DEFINED as its fp32
+ * counterpart applied to x'[f,s,r,i] = y[f,s,r,i] e^{-2 pi i eps_f m / C}, the
+ * f32 value d_eps[f] taken exactly; a non-finite d_eps[f] acts as 0.  The
+ * estimate left in the workspace is the estimate of x': ofdm_frame_export_
+ * estimate, the soft output, ofdm_frame_estimate_denoise and either combine
+ * work on it unchanged (the same fp32 workspace, size and registry rules).
+ *
+ * ofdm_frame_cfo_estimate: gamma_f = sum_s sum_r sum_{i = cp_skip .. cp_len-1}
+ *     conj(y[f,s,r,i]) y[f,s,r,i+C]; d_eps[f] = atan2(Im gamma, Re gamma) /
+ *     2 pi in (-0.5, 0.5], 0 for gamma = 0.  cp_skip leaves out the head of the
+ *     prefix that the previous symbol's echo spoils.  d_gamma (ofdm_cf32
+ *     [nframes]) may be null, d_eps may not.  Any 2 <= C <= 8192; only the
+ *     first and last cp_len samples of each row are read.  Summed in a fixed
+ *     order in float64, no atomics: bit-identical from run to run.
+ *     OFDM_E_ARG, before any device work: cp_len < 1, cp_skip outside
+ *     [0, cp_len), bad geometry as in the other frame entries, a null pointer
+ *     with nframes > 0.  nframes == 0 is a no-op.
+ * ofdm_frame_cfo_derotate: d_out = x' for whole frames, prefix included.
+ *     d_out == d_in is allowed, any other overlap is OFDM_E_ARG.  The route
+ *     for every C without a derotating receiver (as ofdm_iq_convert_sc16 is
+ *     for sc16).  Both buffers 16-byte aligned.
+ * ofdm_frame_estimate_cfo / _combine_cfo / _demod_cfo: the two-launch
+ *     C = 1024 receiver with the rotation applied as each row is loaded (each
+ *     IQ row still read once).  Any other valid C returns OFDM_E_UNSUPPORTED
+ *     before any device work (use ofdm_frame_cfo_derotate and the fp32 entry);
+ *     a null d_eps with nframes > 0 is OFDM_E_ARG.  Sticky device status as in
+ *     the fp32 entries.
+ *   Phase accuracy (the derotator and the fused receiver alike): the phase at
+ *     a symbol's start, eps s (C + cp_len) / C turns, is reduced modulo one
+ *     turn in float64; only the part inside a symbol is formed in f32.
+ * ofdm_pipeline_set_cfo: with on != 0 every later submit estimates eps per
+ *     frame of the chunk (cp_skip as above) into a per-slot device array on
+ *     the compute stream; at C = 1024 it then runs the _cfo receiver, at any
+ *     other C it derotates the slot in place and runs the fp32 forms (with
+ *     ofdm_pipeline_set_denoise also on: estimate -> denoise -> combine in
+ *     their _cfo or derotated forms).  An sc16 pipeline at C != 1024 estimates
+ *     and derotates on its converted fp32 buffer; an sc16 pipeline at
+ *     C = 1024 returns OFDM_E_UNSUPPORTED.  OFDM_E_ARG for a null pipeline
+ *     and, with on != 0, cp_len == 0 or cp_skip outside [0, cp_len).  on == 0
+ *     (the state of a new pipeline): a submit enqueues exactly what it
+ *     enqueues without this call.
+ * Not covered: sc16 x CFO in one kernel, fused derotating receivers for other
+ *     C, the one-launch demod, ofdm_symbols_demod, the antenna-split partials,
+ *     the frequency-domain entries, integer offsets (|eps| >= 0.5: the
+ *     estimator cannot see them), returning the pipeline's estimates to the
+ *     caller, and the host C++ mirrors (host/). */
+int ofdm_frame_cfo_estimate(const ofdm_cf32 *d_iq, long long nframes, int S, int R, int C, int cp_len, int cp_skip,
+                            ofdm_cf32 *d_gamma, float *d_eps, ofdm_stream_t stream);
+int ofdm_frame_cfo_derotate(const ofdm_cf32 *d_in, ofdm_cf32 *d_out, long long nframes, int S, int R, int C,
+                            int cp_len, const float *d_eps, ofdm_stream_t stream);
+int ofdm_frame_estimate_cfo(const ofdm_cf32 *d_iq, long long nframes, int S, int R, int C, int cp_len,
+                            const ofdm_cf32 *d_X, void *d_ws, size_t ws_bytes, const float *d_eps,
+                            ofdm_stream_t stream);
+int ofdm_frame_combine_cfo(const ofdm_cf32 *d_iq, long long nframes, int S, int R, int C, int cp_len, void *d_ws,
+                           size_t ws_bytes, ofdm_cf32 *d_out, const float *d_eps, ofdm_stream_t stream);
+int ofdm_frame_demod_cfo(const ofdm_cf32 *d_iq, long long nframes, int S, int R, int C, int cp_len,
+                         const ofdm_cf32 *d_X, void *d_ws, size_t ws_bytes, ofdm_cf32 *d_out, const float *d_eps,
+                         ofdm_stream_t stream);
+int ofdm_pipeline_set_cfo(ofdm_pipeline *p, int on, int cp_skip);
+
 /* ------------------------------------------------------ PN frame sync --- */
 
 /* Frame synchronisation of the receive driver, on
