@@ -1009,6 +1009,43 @@ int ofdm_frame_soft_demap(const ofdm_cf32 *d_z, long long nframes, int S, int R,
                      fn);
 }
 
+// Phase tracking: every refusal before any device work; the workspace as the
+// soft output takes it (a full estimate of this geometry: P is bin-indexed in
+// all of them), only read.
+int ofdm_frame_phase_track(const ofdm_cf32 *d_z, long long nframes, int S, int R, int C, const void *d_ws,
+                           size_t ws_bytes_, int modulation, ofdm_cf32 *d_out, float *d_phase, ofdm_stream_t stream) {
+    static const char *fn = "ofdm_frame_phase_track";
+    if (modulation != OFDM_MOD_QPSK && modulation != OFDM_MOD_QAM16 && modulation != OFDM_MOD_QAM64 &&
+        modulation != OFDM_MOD_QAM256)
+        return fail(OFDM_E_ARG, "%s: modulation=%d (OFDM_MOD_QPSK 2, _QAM16 4, _QAM64 6 or _QAM256 8)", fn, modulation);
+    if (nframes < 0) return fail(OFDM_E_ARG, "%s: nframes < 0", fn);
+    if (S < 2) return fail(OFDM_E_ARG, "%s: S=%d, a frame needs a pilot and >= 1 data symbol", fn, S);
+    if (R < 1) return fail(OFDM_E_ARG, "%s: R=%d < 1", fn, R);
+    if (!valid_c(C)) return fail(OFDM_E_UNSUPPORTED, "%s: C=%d out of [2, 8192]", fn, C);
+    if (nframes == 0) return OFDM_OK;
+    if (!d_z) return fail(OFDM_E_ARG, "%s: null d_z", fn);
+    if (!d_out) return fail(OFDM_E_ARG, "%s: null d_out", fn);
+    if (!d_ws) return fail(OFDM_E_ARG, "%s: null d_ws", fn);
+    if (!aligned(d_z, 8)) return fail(OFDM_E_ARG, "%s: d_z must be 8-byte aligned", fn);
+    if (!aligned(d_out, 8)) return fail(OFDM_E_ARG, "%s: d_out must be 8-byte aligned", fn);
+    if (!aligned(d_phase, 4)) return fail(OFDM_E_ARG, "%s: d_phase must be 4-byte aligned", fn);
+    const uintptr_t a = reinterpret_cast<uintptr_t>(d_z), b = reinterpret_cast<uintptr_t>(d_out);
+    const uintptr_t bytes = (uintptr_t)nframes * (S - 1) * (C - 1) * sizeof(ofdm_cf32);
+    if (a != b && a < b + bytes && b < a + bytes)
+        return fail(OFDM_E_ARG, "%s: d_out overlaps d_z (in place, d_out == d_z, or disjoint)", fn);
+    if (d_phase) {
+        const uintptr_t p = reinterpret_cast<uintptr_t>(d_phase), pb = (uintptr_t)nframes * (S - 1) * sizeof(float);
+        if ((p < a + bytes && a < p + pb) || (p < b + bytes && b < p + pb))
+            return fail(OFDM_E_ARG, "%s: d_phase overlaps d_z or d_out", fn);
+    }
+    int rc = ws_check(d_ws, ws_bytes_, nframes, S, R, C, true, fn);
+    if (rc) return rc;
+    Workspace w;
+    if ((rc = carve(const_cast<void *>(d_ws), ws_bytes_, nframes, S, R, C, !fused_c(C), w))) return rc;
+    return hip_check(ofdm::launch_phase_track(F2(d_z), nframes, S, C, w.P, modulation, F2(d_out), d_phase, hs(stream)),
+                     fn);
+}
+
 int ofdm_synth_frames(ofdm_cf32 *d_iq, long long nframes, int S, int R, int C, int prefix,
                       const ofdm_cf32 *d_X, unsigned long long seed, long long frame0,
                       float noise_std, int freq_domain, int r0, ofdm_stream_t stream) {

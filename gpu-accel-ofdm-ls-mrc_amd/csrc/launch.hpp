@@ -220,6 +220,13 @@ hipError_t launch_noise_estimate(const float2 *z, long long nframes, int S, int 
 hipError_t launch_soft_demap(const float2 *z, long long nframes, int S, int C, const float *P, const float *nv,
                              int bps, int fmt, float llr_scale, void *out, hipStream_t s);
 
+// Decision-directed phase tracking (phase_track.hip states the recursion).
+// z, out: [nframes][S-1][K] (8-B aligned; out == z or disjoint), P: the
+// workspace's bin-indexed |H|^2 [nframes][C], bps in {2, 4, 6, 8}, phase:
+// [nframes][S-1] radians, unwrapped (may be null).  2 <= C <= 8192, S >= 2.
+hipError_t launch_phase_track(const float2 *z, long long nframes, int S, int C, const float *P, int bps, float2 *out,
+                              float *phase, hipStream_t s);
+
 // OFDM modulator (tx_mod.hip; any C but 1024: fft_any.hip k_tx_any): row i =
 // X + i*ldx (K values, through the bin placement `map`) -> backward FFT ->
 // iq + i*(C+cp): the last cp samples, then the C samples, times 1/peak

@@ -42,6 +42,7 @@ struct ofdm_pipeline {
     int taps_post = 0, taps_pre = 0;  // ofdm_pipeline_set_denoise; taps_post == 0: off
     bool cfo = false;                 // ofdm_pipeline_set_cfo
     int cp_skip = 0;
+    int phase_mod = 0;                // ofdm_pipeline_set_phase_track; 0: off
     long long chunk = 0;
     size_t ws_bytes = 0, frame_in = 0, frame_out = 0;  // elements
     ofdm_cf32 *X = nullptr;
@@ -332,6 +333,12 @@ int ofdm_pipeline_submit(ofdm_pipeline *p, long long nframes, ofdm_cf32 *out) {
         }
         if (rc) return rc;
     }
+    if (nframes > 0 && p->phase_mod) {
+        // whichever receiver form ran above left its estimate in the slot's workspace
+        int rc = ofdm_frame_phase_track(s.out, nframes, p->S, p->R, p->C, s.ws, p->ws_bytes, p->phase_mod, s.out, nullptr,
+                                        p->s_comp);
+        if (rc) return rc;
+    }
     PL_TRY(hipEventRecord(s.comp_done, p->s_comp), fn, "hipEventRecord");
     PL_TRY(hipStreamWaitEvent(p->s_out, s.comp_done, 0), fn, "hipStreamWaitEvent");
     if (out && nframes > 0)
@@ -374,6 +381,16 @@ int ofdm_pipeline_set_cfo(ofdm_pipeline *p, int on, int cp_skip) {
         if (!s.eps) PL_TRY(hipMalloc(&s.eps, (size_t)p->chunk * sizeof(float)), fn, "hipMalloc(eps slot)");
     p->cfo = true;
     p->cp_skip = cp_skip;
+    return OFDM_OK;
+}
+
+int ofdm_pipeline_set_phase_track(ofdm_pipeline *p, int modulation) {
+    static const char *fn = "ofdm_pipeline_set_phase_track";
+    if (!p) return err(OFDM_E_ARG, fn, "null pipeline");
+    if (modulation != 0 && modulation != OFDM_MOD_QPSK && modulation != OFDM_MOD_QAM16 && modulation != OFDM_MOD_QAM64 &&
+        modulation != OFDM_MOD_QAM256)
+        return err(OFDM_E_ARG, fn, "modulation must be 0 (off), 2, 4, 6 or 8");
+    p->phase_mod = modulation;
     return OFDM_OK;
 }
 

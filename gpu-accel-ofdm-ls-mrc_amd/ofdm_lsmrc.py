@@ -86,6 +86,8 @@ _SIGS = {
     "ofdm_frame_combine_cfo": (_I, [_P, _LL, _I, _I, _I, _I, _P, _c.c_size_t, _P, _P, _P]),
     "ofdm_frame_demod_cfo": (_I, [_P, _LL, _I, _I, _I, _I, _P, _P, _c.c_size_t, _P, _P, _P]),
     "ofdm_pipeline_set_cfo": (_I, [_P, _I, _I]),
+    "ofdm_frame_phase_track": (_I, [_P, _LL, _I, _I, _I, _P, _c.c_size_t, _I, _P, _P, _P]),
+    "ofdm_pipeline_set_phase_track": (_I, [_P, _I]),
     "ofdm_host_register": (_I, [_P, _c.c_size_t]),
     "ofdm_host_unregister": (_I, [_P]),
     "ofdm_pn_correlate": (_I, [_P, _I, _LL, _P, _I, _c.c_float, _P, _P, _P]),
@@ -654,6 +656,41 @@ def frame_soft_demap(z, ws, F, S, R, C, modulation, noise_var, fmt="f32", scale=
     return out
 
 
+def frame_phase_track(z, ws, F, S, R, C, modulation, out=None, phase=None, stream=None):
+    """Decision-directed phase tracking of the demodulated symbols z
+    (F, S-1, K) -> the derotated (F, S-1, K); out=z works in place.  P comes
+    from the estimate in ws (any full estimate of this F, S, R, C).  phase
+    (F, S-1) float32, when given, receives the tracked phase of every data
+    symbol in radians, unwrapped (include/ofdm_lsmrc.h, "phase tracking")."""
+    import torch
+    if out is None:
+        out = c64((F, S - 1, C - 1), z.device)
+    if phase is not None and (not isinstance(phase, torch.Tensor) or phase.dtype != torch.float32
+                              or tuple(phase.shape) != (F, S - 1)):
+        raise OfdmError(f"phase must be a torch.float32 tensor of shape ({F}, {S - 1})")
+    _check(lib().ofdm_frame_phase_track(_dptr(z, "z") if F else None, F, S, R, C, _dptr(ws, "ws") if F else None,
+                                        ws.numel() if F else 0, modulation, _dptr(out, "out") if F else None,
+                                        _dptr(phase, "phase") if F and phase is not None else None, _stream(stream)),
+           "ofdm_frame_phase_track")
+    return out
+
+
+def residual_cfo(phase, C, prefix):
+    """The carrier frequency offset a frame's tracked phases show, per frame, in
+    subcarrier spacings: the least-squares slope through the origin of
+    theta over n' = 1 .. S-1 (the pilot is phase 0), sum n' theta / sum n'^2,
+    times C / (2 pi (C + prefix)).  phase: (F, S-1) torch tensor or numpy
+    array, as frame_phase_track wrote it; the result is of the same kind,
+    float64.  No kernel."""
+    k = C / (2.0 * np.pi * (C + prefix))
+    if isinstance(phase, np.ndarray):
+        n = np.arange(1, phase.shape[-1] + 1, dtype=np.float64)
+        return (phase.astype(np.float64) * n).sum(-1) / (n * n).sum() * k
+    import torch
+    n = torch.arange(1, phase.shape[-1] + 1, dtype=torch.float64, device=phase.device)
+    return (phase.to(torch.float64) * n).sum(-1) / (n * n).sum() * k
+
+
 def synth_frames(F, S, R, C, X, prefix=0, seed=1234, frame0=0, noise_std=0.01,
                  freq_domain=False, r0=0, out=None, stream=None):
     Cp = C if freq_domain else C + prefix
@@ -884,6 +921,12 @@ class Pipeline:
         receiver at C = 1024, frame_cfo_derotate on the slot at any other C.
         on=False turns it off again (the default)."""
         _check(lib().ofdm_pipeline_set_cfo(self._h, int(bool(on)), cp_skip), "ofdm_pipeline_set_cfo")
+
+    def set_phase_track(self, modulation):
+        """Later submits run frame_phase_track in place on the slot's output
+        (modulation 2, 4, 6 or 8), after whichever receiver form the submit
+        used and before the copy-out; 0 turns it off again (the default)."""
+        _check(lib().ofdm_pipeline_set_phase_track(self._h, modulation), "ofdm_pipeline_set_phase_track")
 
     def close(self):
         if getattr(self, "_h", None):

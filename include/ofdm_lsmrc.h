@@ -574,6 +574,64 @@ int ofdm_frame_demod_cfo(const ofdm_cf32 *d_iq, long long nframes, int S, int R,
                          ofdm_stream_t stream);
 int ofdm_pipeline_set_cfo(ofdm_pipeline *p, int on, int cp_skip);
 
+/* ------------------------------------------------------ phase tracking --- */
+
+/* Decision-directed carrier phase tracking between the combiner and the
+ * demapper (no reference counterpart; added without a version step:
+ * OFDM_LSMRC_VERSION stays 2).  A frame is one pilot and then up to 100 data
+ * symbols combined against that one estimate: whatever offset the prefix
+ * estimator leaves, eps_res, turns every later symbol by a further
+ * 2 pi eps_res (C + cp_len) / C, and oscillator phase noise adds to it.
+ *
+ * ofdm_frame_phase_track reads d_z, the demodulated [nframes][S-1][K] array of
+ * a frame call (rotated order), and the |H|^2 sums P its estimate left in
+ * d_ws (as the soft output reads them: P[f][j(k)], j(k) the subcarrier at
+ * output position k), and writes the derotated array d_out and, if d_phase is
+ * not null, the tracked phase of every data symbol.  For frame f the rows
+ * n = 0 .. S-2 (data symbols 1 .. S-1) are processed in order from
+ * theta_(-1) = theta_(-2) = 0 (the pilot symbol is phase 0 by construction):
+ *   1. phi = theta_(n-1) + (theta_(n-1) - theta_(n-2))
+ *      (linear extrapolation: a constant drift costs nothing)
+ *   2. w_k = z_k e^{-i phi},  d_k = slice(w_k), the nearest point of the
+ *      38.211 constellation (`modulation` as in the soft output): per axis
+ *      t = clamp(floor(x / 2a), -L, L-1), L = 2^(bps/2 - 1), point a (2t + 1)
+ *   3. g = sum_k P[f][j(k)] w_k conj(d_k); elements whose P is not positive
+ *      and finite are skipped.  Fixed-order reduction, no atomics:
+ *      bit-identical from run to run.
+ *   4. delta = atan2(Im g, Re g), 0 when g is 0 or not finite (one bad symbol
+ *      does not poison the rest of the frame);  theta_n = phi + delta
+ *   5. d_out[f][n][k] = z_k e^{-i theta_n} for every k, skipped elements
+ *      included;  d_phase[f*(S-1) + n] = theta_n in radians, unwrapped
+ *      (cumulative: tens of radians over 100 symbols), f32.
+ * theta is carried in float64; only its value modulo one turn goes through
+ * an f32 sincos.  The slope of d_phase over a frame gives the residual offset
+ * back: eps_res = sum_n' n' theta_(n'-1) / sum_n' n'^2 * C / (2 pi (C + cp_len)),
+ * n' = 1 .. S-1.
+ * d_z and d_out: 8-byte aligned, d_out == d_z (in place) or disjoint; d_phase
+ * disjoint from both.  The workspace goes through the registry as for
+ * ofdm_frame_soft_demap: any FULL estimate of the same nframes, S, R, C,
+ * ws_bytes; it is only read, no work tickets, and the sticky device status is
+ * neither consulted nor cleared.  Before any device work: OFDM_E_ARG for a
+ * modulation not listed, nframes < 0, S < 2, R < 1, a null or misaligned d_z,
+ * d_out or d_ws with nframes > 0, buffers that overlap otherwise, an
+ * antenna-split partial estimate, another geometry or a workspace without an
+ * estimate; OFDM_E_UNSUPPORTED for C outside [2, 8192].  nframes == 0 is a
+ * no-op (OFDM_OK).
+ *
+ * ofdm_pipeline_set_phase_track: with modulation 2, 4, 6 or 8 every later
+ * submit runs the tracker in place on the slot's output, on the compute
+ * stream, after whichever receiver form the submit used (fp32, sc16, CFO,
+ * denoise) and before the copy-out.  0 turns it off (the state of a new
+ * pipeline): a submit then enqueues exactly what it enqueues without this
+ * call.  OFDM_E_ARG for a null pipeline or another modulation.  The
+ * per-symbol phases are not handed back (as the CFO estimates are not).
+ * Not covered: the tracker fused into the receivers' epilogues, tracking on
+ * pilot subcarriers, and returning the pipeline's phases. */
+int ofdm_frame_phase_track(const ofdm_cf32 *d_z, long long nframes, int S, int R, int C, const void *d_ws,
+                           size_t ws_bytes, int modulation, ofdm_cf32 *d_out,
+                           float *d_phase /* [nframes][S-1] or NULL */, ofdm_stream_t stream);
+int ofdm_pipeline_set_phase_track(ofdm_pipeline *p, int modulation);
+
 /* ------------------------------------------------------ PN frame sync --- */
 
 /* Frame synchronisation of the receive driver, on
