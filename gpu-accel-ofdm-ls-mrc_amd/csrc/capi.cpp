@@ -57,7 +57,7 @@ bool lane_c(int C) { return fused_c(C) || ofdm::lane512_supported(C); }
 // fused time-domain kernels by C (fused_c(C) must hold)
 hipError_t ls_fused(const float2 *iq, long long F, int S, int R, int C, int prefix, const float2 *X,
                     float2 *Hc, float *P, int partial, hipStream_t s) {
-    if (C == 1024) return ofdm::launch_ls_td1024(iq, F, S, R, prefix, X, Hc, P, partial, s);
+    if (C == 1024) return ofdm::launch_ls_td1024(ofdm::iq_f32(iq), F, S, R, prefix, X, Hc, P, partial, s);
     if (C == 2048) return ofdm::launch_ls_td2048(iq, F, S, R, prefix, X, Hc, P, partial, s);
     return ofdm::launch_ls_td4096(iq, F, S, R, prefix, X, Hc, P, partial, s);
 }
@@ -65,7 +65,7 @@ hipError_t tickets_for(unsigned long long *area, hipStream_t s, ofdm::Tickets *t
 // tickets: the frame workspace's ticket area (work-ticketed kernels: C = 2048 and 4096)
 hipError_t mrc_fused(const float2 *iq, long long F, int S, int R, int C, int prefix, const float2 *Hc,
                      const float *P, float2 *out, int mode, hipStream_t s, unsigned long long *tickets) {
-    if (C == 1024) return ofdm::launch_mrc_td1024(iq, F, S, R, prefix, Hc, P, out, mode, s);
+    if (C == 1024) return ofdm::launch_mrc_td1024(ofdm::iq_f32(iq), F, S, R, prefix, Hc, P, out, mode, s);
     ofdm::Tickets tk;
     if (hipError_t e = tickets_for(tickets, s, &tk); e != hipSuccess) return e;
     return C == 2048 ? ofdm::launch_mrc_td2048(iq, F, S, R, prefix, Hc, P, out, mode, tk, s)
@@ -552,6 +552,47 @@ int ofdm_frame_demod_ex(const ofdm_cf32 *d_iq, long long nframes, int S, int R, 
     return rc;
 }
 
+// The sc16 and CFO frame entries (C = 1024, two launches) behind their own
+// argument checks: what the fp32 entries do at a fused C, on the entry's
+// sample source.
+static int ls_1024(const ofdm::Iq1024 &src, long long nframes, int S, int R, int prefix, const ofdm_cf32 *d_X,
+                   void *d_ws, size_t ws_bytes_, const Workspace &w, hipStream_t s) {
+    ws_forget(d_ws);
+    int rc = hip_check(ofdm::launch_ls_td1024(src, nframes, S, R, prefix, F2(d_X), w.Hc, w.P, 0, s),
+                       src.i16 ? "ls_td1024_sc16" : "ls_td1024_cfo");
+    // the estimate is in the workspace once the LS launch is enqueued
+    if (rc == OFDM_OK) ws_record(d_ws, ws_bytes_, nframes, S, R, 1024, true, false);
+    return rc;
+}
+static int mrc_1024(const ofdm::Iq1024 &src, long long nframes, int S, int R, int prefix, const Workspace &w,
+                    ofdm_cf32 *d_out, hipStream_t s) {
+    return hip_check(ofdm::launch_mrc_td1024(src, nframes, S, R, prefix, w.Hc, w.P, F2(d_out), 0, s),
+                     src.i16 ? "mrc_td1024_sc16" : "mrc_td1024_cfo");
+}
+static int estimate_1024(const ofdm::Iq1024 &src, long long nframes, int S, int R, int prefix, const ofdm_cf32 *d_X,
+                         void *d_ws, size_t ws_bytes_, ofdm_stream_t stream) {
+    Workspace w;
+    if (int rc = carve(d_ws, ws_bytes_, nframes, S, R, 1024, false, w)) return rc;
+    return ls_1024(src, nframes, S, R, prefix, d_X, d_ws, ws_bytes_, w, hs(stream));
+}
+static int combine_1024(const char *fn, const ofdm::Iq1024 &src, long long nframes, int S, int R, int prefix,
+                        void *d_ws, size_t ws_bytes_, ofdm_cf32 *d_out, ofdm_stream_t stream) {
+    WsTag tag;
+    if (int rc = ws_check(d_ws, ws_bytes_, nframes, S, R, 1024, true, fn, &tag)) return rc;
+    if (!tag.lane_order)
+        return fail(OFDM_E_ARG, "%s: the workspace holds a frequency-domain estimate (use ofdm_frame_combine_freq)", fn);
+    Workspace w;
+    if (int rc = carve(d_ws, ws_bytes_, nframes, S, R, 1024, false, w)) return rc;
+    return mrc_1024(src, nframes, S, R, prefix, w, d_out, hs(stream));
+}
+static int demod_1024(const ofdm::Iq1024 &src, long long nframes, int S, int R, int prefix, const ofdm_cf32 *d_X,
+                      void *d_ws, size_t ws_bytes_, ofdm_cf32 *d_out, ofdm_stream_t stream) {
+    Workspace w;
+    if (int rc = carve(d_ws, ws_bytes_, nframes, S, R, 1024, false, w)) return rc;
+    if (int rc = ls_1024(src, nframes, S, R, prefix, d_X, d_ws, ws_bytes_, w, hs(stream))) return rc;
+    return mrc_1024(src, nframes, S, R, prefix, w, d_out, hs(stream));
+}
+
 // sc16 IQ: the checks every sc16 frame entry makes after check_frame_args,
 // before any HIP call.
 static int check_sc16(const char *fn, float scale, int C) {
@@ -584,14 +625,7 @@ int ofdm_frame_estimate_sc16(const ofdm_sc16 *d_iq, long long nframes, int S, in
     if ((rc = check_sc16(fn, scale, C))) return rc;
     if (!d_X) return fail(OFDM_E_ARG, "%s: null pilots", fn);
     if (nframes == 0) return OFDM_OK;
-    Workspace w;
-    if ((rc = carve(d_ws, ws_bytes_, nframes, S, R, C, false, w))) return rc;
-    ws_forget(d_ws);
-    rc = hip_check(ofdm::launch_ls_td1024_sc16(SC(d_iq), nframes, S, R, prefix, scale, F2(d_X), w.Hc, w.P, 0,
-                                               hs(stream)),
-                   "ls_td1024_sc16");
-    if (rc == OFDM_OK) ws_record(d_ws, ws_bytes_, nframes, S, R, C, true, false);
-    return rc;
+    return estimate_1024(ofdm::iq_sc16(SC(d_iq), scale), nframes, S, R, prefix, d_X, d_ws, ws_bytes_, stream);
 }
 
 int ofdm_frame_combine_sc16(const ofdm_sc16 *d_iq, long long nframes, int S, int R, int C, int prefix, float scale,
@@ -602,15 +636,7 @@ int ofdm_frame_combine_sc16(const ofdm_sc16 *d_iq, long long nframes, int S, int
     if (rc) return rc;
     if ((rc = check_sc16(fn, scale, C))) return rc;
     if (nframes == 0) return OFDM_OK;
-    WsTag tag;
-    if ((rc = ws_check(d_ws, ws_bytes_, nframes, S, R, C, true, fn, &tag))) return rc;
-    if (!tag.lane_order)
-        return fail(OFDM_E_ARG, "%s: the workspace holds a frequency-domain estimate (use ofdm_frame_combine_freq)", fn);
-    Workspace w;
-    if ((rc = carve(d_ws, ws_bytes_, nframes, S, R, C, false, w))) return rc;
-    return hip_check(ofdm::launch_mrc_td1024_sc16(SC(d_iq), nframes, S, R, prefix, scale, w.Hc, w.P, F2(d_out), 0,
-                                                  hs(stream)),
-                     "mrc_td1024_sc16");
+    return combine_1024(fn, ofdm::iq_sc16(SC(d_iq), scale), nframes, S, R, prefix, d_ws, ws_bytes_, d_out, stream);
 }
 
 int ofdm_frame_demod_sc16(const ofdm_sc16 *d_iq, long long nframes, int S, int R, int C, int prefix, float scale,
@@ -622,17 +648,7 @@ int ofdm_frame_demod_sc16(const ofdm_sc16 *d_iq, long long nframes, int S, int R
     if ((rc = check_sc16(fn, scale, C))) return rc;
     if (!d_X) return fail(OFDM_E_ARG, "%s: null pilots", fn);
     if (nframes == 0) return OFDM_OK;
-    Workspace w;
-    if ((rc = carve(d_ws, ws_bytes_, nframes, S, R, C, false, w))) return rc;
-    hipStream_t s = hs(stream);
-    ws_forget(d_ws);
-    rc = hip_check(ofdm::launch_ls_td1024_sc16(SC(d_iq), nframes, S, R, prefix, scale, F2(d_X), w.Hc, w.P, 0, s),
-                   "ls_td1024_sc16");
-    if (rc) return rc;
-    // the estimate is in the workspace once the LS launch is enqueued
-    ws_record(d_ws, ws_bytes_, nframes, S, R, C, true, false);
-    return hip_check(ofdm::launch_mrc_td1024_sc16(SC(d_iq), nframes, S, R, prefix, scale, w.Hc, w.P, F2(d_out), 0, s),
-                     "mrc_td1024_sc16");
+    return demod_1024(ofdm::iq_sc16(SC(d_iq), scale), nframes, S, R, prefix, d_X, d_ws, ws_bytes_, d_out, stream);
 }
 
 // Carrier frequency offset: the checks every *_cfo receiver entry makes after
@@ -683,13 +699,7 @@ int ofdm_frame_estimate_cfo(const ofdm_cf32 *d_iq, long long nframes, int S, int
     if ((rc = check_cfo(fn, nframes, d_eps, C))) return rc;
     if (!d_X) return fail(OFDM_E_ARG, "%s: null pilots", fn);
     if (nframes == 0) return OFDM_OK;
-    Workspace w;
-    if ((rc = carve(d_ws, ws_bytes_, nframes, S, R, C, false, w))) return rc;
-    ws_forget(d_ws);
-    rc = hip_check(ofdm::launch_ls_td1024_cfo(F2(d_iq), nframes, S, R, prefix, d_eps, F2(d_X), w.Hc, w.P, hs(stream)),
-                   "ls_td1024_cfo");
-    if (rc == OFDM_OK) ws_record(d_ws, ws_bytes_, nframes, S, R, C, true, false);
-    return rc;
+    return estimate_1024(ofdm::iq_f32(F2(d_iq), d_eps), nframes, S, R, prefix, d_X, d_ws, ws_bytes_, stream);
 }
 
 int ofdm_frame_combine_cfo(const ofdm_cf32 *d_iq, long long nframes, int S, int R, int C, int prefix, void *d_ws,
@@ -700,15 +710,7 @@ int ofdm_frame_combine_cfo(const ofdm_cf32 *d_iq, long long nframes, int S, int 
     if (rc) return rc;
     if ((rc = check_cfo(fn, nframes, d_eps, C))) return rc;
     if (nframes == 0) return OFDM_OK;
-    WsTag tag;
-    if ((rc = ws_check(d_ws, ws_bytes_, nframes, S, R, C, true, fn, &tag))) return rc;
-    if (!tag.lane_order)
-        return fail(OFDM_E_ARG, "%s: the workspace holds a frequency-domain estimate (use ofdm_frame_combine_freq)", fn);
-    Workspace w;
-    if ((rc = carve(d_ws, ws_bytes_, nframes, S, R, C, false, w))) return rc;
-    return hip_check(ofdm::launch_mrc_td1024_cfo(F2(d_iq), nframes, S, R, prefix, d_eps, w.Hc, w.P, F2(d_out),
-                                                 hs(stream)),
-                     "mrc_td1024_cfo");
+    return combine_1024(fn, ofdm::iq_f32(F2(d_iq), d_eps), nframes, S, R, prefix, d_ws, ws_bytes_, d_out, stream);
 }
 
 int ofdm_frame_demod_cfo(const ofdm_cf32 *d_iq, long long nframes, int S, int R, int C, int prefix,
@@ -721,17 +723,7 @@ int ofdm_frame_demod_cfo(const ofdm_cf32 *d_iq, long long nframes, int S, int R,
     if ((rc = check_cfo(fn, nframes, d_eps, C))) return rc;
     if (!d_X) return fail(OFDM_E_ARG, "%s: null pilots", fn);
     if (nframes == 0) return OFDM_OK;
-    Workspace w;
-    if ((rc = carve(d_ws, ws_bytes_, nframes, S, R, C, false, w))) return rc;
-    hipStream_t s = hs(stream);
-    ws_forget(d_ws);
-    rc = hip_check(ofdm::launch_ls_td1024_cfo(F2(d_iq), nframes, S, R, prefix, d_eps, F2(d_X), w.Hc, w.P, s),
-                   "ls_td1024_cfo");
-    if (rc) return rc;
-    // the estimate is in the workspace once the LS launch is enqueued
-    ws_record(d_ws, ws_bytes_, nframes, S, R, C, true, false);
-    return hip_check(ofdm::launch_mrc_td1024_cfo(F2(d_iq), nframes, S, R, prefix, d_eps, w.Hc, w.P, F2(d_out), s),
-                     "mrc_td1024_cfo");
+    return demod_1024(ofdm::iq_f32(F2(d_iq), d_eps), nframes, S, R, prefix, d_X, d_ws, ws_bytes_, d_out, stream);
 }
 
 int ofdm_frame_estimate_freq(const ofdm_cf32 *d_Y, long long nframes, int S, int R, int C,

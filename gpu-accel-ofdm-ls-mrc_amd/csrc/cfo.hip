@@ -31,7 +31,7 @@
 //                   8-B aligned when C + cp is odd: a leading / trailing sample
 //                   goes alone).
 // The fused C = 1024 receiver with the rotation in is frame_td.hip's
-// (k_ls_td1024_cfo, k_mrc_td1024_hlds_cfo); this derotator is the route for
+// (k_ls_td1024 / k_mrc_td1024_hlds under src_cfo); this derotator is the route for
 // every other C.
 #include "common.hpp"
 #include "launch.hpp"

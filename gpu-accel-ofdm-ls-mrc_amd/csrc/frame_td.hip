@@ -52,7 +52,7 @@ namespace td1024 {
 constexpr int LS_WAVES = 4;
 
 // ---------------------------------------------------------------------------
-// Carrier frequency offset (cfo.hip states the convention): the _cfo kernels
+// Carrier frequency offset (cfo.hip states the convention): the src_cfo kernels
 // transform x'[n] = y[n] e^{-2 pi i eps (m0 + n) / C}, m0 = s (C + prefix) +
 // prefix the frame-sample index of the symbol's first FFT sample.  Lane t holds
 // n = t + 64 m, so the rotation of a row splits three ways:
@@ -72,11 +72,33 @@ constexpr int LS_WAVES = 4;
 //                             otherwise (a straddling MRC workgroup) each
 //                             twiddle is multiplied by it from two registers.
 // A non-finite eps acts as 0.
+//
+// The rotation is a compile-time policy of the C = 1024 kernels and row
+// functions (SRC = src_cfo), not a copy of them.  Every `if constexpr (CFO<...>)`
+// site must leave the src_plain instantiations with no CFO state at all -- no
+// Rot, no eps, no phase: an empty NoRot is passed, never a Rot of ones -- so
+// that their code stays what it was without the policy.  Checked when the
+// policy went in by comparing the gfx950 instruction streams of the seven
+// src_plain kernels with those of the separate kernels before it (DESIGN.md
+// 4.13): same mnemonics, same registers, operands equal up to the source order
+// of commutative adds.  A change to one of these sites repeats that comparison.
 // ---------------------------------------------------------------------------
 struct Rot {
     float2 l;               // e^{-2 pi i eps t / C} of this lane
     float cr[15], ci[15];   // e^{-2 pi i eps 64 m / C}, m = 1..15 (wave-uniform)
 };
+struct NoRot {};
+// The sample-source policy and what the kernels' last argument is under it.
+struct src_plain {
+    using arg = float;  // the sc16 scale (ignored for float2)
+    using rot = NoRot;
+};
+struct src_cfo {
+    using arg = const float *__restrict__;  // eps: one offset per frame
+    using rot = Rot;
+};
+template <class T>
+constexpr bool CFO = __is_same(T, src_cfo) || __is_same(T, Rot);
 
 __device__ __forceinline__ float cfo_eps(const float *eps, long long f) {
     const float e = eps[f];
@@ -115,7 +137,7 @@ __device__ __forceinline__ void rot_row(float2 (&a)[16], const Rot &rot) {
     for (int m = 1; m < 16; ++m) a[m] = cmul(a[m], float2{rot.cr[m - 1], rot.ci[m - 1]});
 }
 // row_fft (wave_fft1024.hpp) of the rotated row; tw's first table carries the
-// lane factor in every entry, k2 = 0 included (k_ls_td1024_cfo folds it in)
+// lane factor in every entry, k2 = 0 included (k_ls_td1024 folds it in)
 __device__ __forceinline__ void row_fft_rot(float2 (&a)[16], int t, float2 *T, const float2 *tw, const Rot &rot,
                                             float2 (&x)[16]) {
     rot_row(a, rot);
@@ -138,17 +160,29 @@ __device__ __forceinline__ void row_fft_rot(float2 (&a)[16], int t, float2 *T, c
     quad_dft(x, qa);
 }
 
-template <int NW, class IQ>
+// SRC = src_cfo: the estimate of x' (fp32 rows; `last` is eps).
+template <int NW, class IQ, class SRC>
 __global__ void __launch_bounds__(64 * NW) k_ls_td1024(const IQ *__restrict__ iq, int S, int R,
                                                        int prefix, const float2 *__restrict__ X,
                                                        float2 *__restrict__ Hc, float *__restrict__ P,
-                                                       int partial, float scale) {
+                                                       int partial, typename SRC::arg last) {
+    static_assert(!(CFO<SRC> && is_sc16<IQ>), "the CFO policy covers fp32 rows");
     extern __shared__ __attribute__((aligned(16))) float2 lds[];
     float2 *tw = lds;
     const int w = threadIdx.x >> 6;
     const int t = threadIdx.x & 63;
     float2 *T = lds + TWBUF + w * TBUF;
     fill_twiddles(tw);
+    [[maybe_unused]] typename SRC::rot rot;
+    [[maybe_unused]] float2 p0;
+    if constexpr (CFO<SRC>) {
+        const float e = uniform_f(cfo_eps(last, blockIdx.x));
+        // the lane factor into the table entries this thread has just written
+        for (int i = threadIdx.x; i < TW1BUF; i += blockDim.x)
+            if (i % TW1P < 16) tw[i] = cmul(tw[i], cis_turns(-e * (float)(i / TW1P) * (1.f / C)));
+        rot = make_rot(e, t);
+        p0 = cfo_symbol_phase(e, prefix, 1.f);  // conj(Y' / X) = conj(Y / X) e^{+2 pi i eps prefix / C}
+    }
     __syncthreads();
 
     const long long f = blockIdx.x;
@@ -174,75 +208,15 @@ __global__ void __launch_bounds__(64 * NW) k_ls_td1024(const IQ *__restrict__ iq
         } else {
             row_load(pilot + (long long)r * Cp, t, a);
         }
-        row_fft(a, t, T, tw, x);
+        if constexpr (CFO<SRC>)
+            row_fft_rot(a, t, T, tw, rot, x);
+        else
+            row_fft(a, t, T, tw, x);
 #pragma unroll
         for (int k = 0; k < 16; ++k) {
             float2 h = ls_conj(x[k], xp[k]);
-            if constexpr (is_sc16<IQ>) h = float2{h.x * scale, h.y * scale};
-            if (b0 + 16 * k == 0) h = float2{0.f, 0.f};
-            x[k] = h;
-            p[k] = p[k] + (h.x * h.x) + (h.y * h.y);
-        }
-        hc_store(Hf + (long long)r * (C / 2), t, x);
-    }
-    __syncthreads();
-    float *pp = reinterpret_cast<float *>(lds + TWBUF);  // [NW][C], reuses T
-    static_assert(NW * C * sizeof(float) <= NW * TBUF * sizeof(float2), "partials fit the transpose images");
-#pragma unroll
-    for (int k = 0; k < 16; ++k) pp[w * C + b0 + 16 * k] = p[k];
-    __syncthreads();
-    float *Pf = P + f * C;
-    const int nw = R < NW ? R : NW;  // waves that hold rows
-    for (int b = threadIdx.x; b < C; b += blockDim.x) {
-        float sum = pp[b];
-        for (int i = 1; i < nw; ++i) sum = sum + pp[i * C + b];
-        Pf[b] = b == 0 ? (partial ? 0.f : 1.f) : sum;
-    }
-}
-
-// k_ls_td1024<NW, float2> on x' (eps: one offset per frame): the same body
-// with the rotation in -- a kernel of its own, so that the others' code
-// generation is not touched.
-template <int NW>
-__global__ void __launch_bounds__(64 * NW) k_ls_td1024_cfo(const float2 *__restrict__ iq, int S, int R,
-                                                           int prefix, const float2 *__restrict__ X,
-                                                           float2 *__restrict__ Hc, float *__restrict__ P,
-                                                           int partial, const float *__restrict__ eps) {
-    extern __shared__ __attribute__((aligned(16))) float2 lds[];
-    float2 *tw = lds;
-    const int w = threadIdx.x >> 6;
-    const int t = threadIdx.x & 63;
-    float2 *T = lds + TWBUF + w * TBUF;
-    fill_twiddles(tw);
-    const float e = uniform_f(cfo_eps(eps, blockIdx.x));
-    // the lane factor into the table entries this thread has just written
-    for (int i = threadIdx.x; i < TW1BUF; i += blockDim.x)
-        if (i % TW1P < 16) tw[i] = cmul(tw[i], cis_turns(-e * (float)(i / TW1P) * (1.f / C)));
-    const Rot rot = make_rot(e, t);
-    const float2 p0 = cfo_symbol_phase(e, prefix, 1.f);  // conj(Y' / X) = conj(Y / X) e^{+2 pi i eps prefix / C}
-    __syncthreads();
-
-    const long long f = blockIdx.x;
-    const int Cp = C + prefix;
-    const float2 *pilot = iq + f * (long long)S * R * Cp + prefix;
-    float4 *Hf = reinterpret_cast<float4 *>(Hc + f * (long long)R * C);
-    const int b0 = lane_bin0(t);
-    float2 xp[16];  // rotated pilots of this lane's subcarriers
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-        const int b = b0 + 16 * k;
-        xp[k] = b > 0 ? X[b - 1] : float2{1.f, 0.f};
-    }
-    float p[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) p[k] = 0.f;
-    for (int r = w; r < R; r += NW) {
-        float2 a[16], x[16];
-        row_load(pilot + (long long)r * Cp, t, a);
-        row_fft_rot(a, t, T, tw, rot, x);
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            float2 h = cmul(ls_conj(x[k], xp[k]), p0);
+            if constexpr (is_sc16<IQ>) h = float2{h.x * last, h.y * last};
+            if constexpr (CFO<SRC>) h = cmul(h, p0);
             if (b0 + 16 * k == 0) h = float2{0.f, 0.f};
             x[k] = h;
             p[k] = p[k] + (h.x * h.x) + (h.y * h.y);
@@ -379,20 +353,24 @@ __device__ __forceinline__ void hlds_row_pf(const IQ *next, __amdgpu_buffer_rsrc
 // The scheduler barriers pin each piece to its place and keep the second FFT
 // half in front of the exchange (left free in the sc16 loop, the scheduler
 // moved it between the two barriers and the allocator spilled accumulators).
+// ROT = Rot: the row rotated (fft_a_rot<true>: tw1 with the lane factor folded in).
 constexpr int PP_A = 4, PP_B = 8, PP_C = 4;
-template <bool PREF, class IQ>
+template <bool PREF, class IQ, class ROT>
 __device__ __forceinline__ void hlds_row_pp(const IQ *next, __amdgpu_buffer_rsrc_t hc, int hoff, int t,
                                             row_reg_t<IQ> (&cur)[16], row_reg_t<IQ> (&nxt)[16],
                                             float2 *T, const float2 *tw1, const float2 *tw2,
                                             const float4 *lo, const float4 *hi, float4 *mine,
-                                            float2 (&acc)[16]) {
+                                            float2 (&acc)[16], const ROT &rot) {
     using namespace hlds;
     static_assert(PP_A >= 0 && PP_B >= 0 && PP_C >= 0 && PP_A + PP_B + PP_C <= 16, "the row's 16 loads");
     const float4 hreg = __builtin_bit_cast(float4, (v4i_t)__builtin_amdgcn_raw_buffer_load_b128(hc, t * 16, hoff, 0));
     if (PREF) row_load_part<0, PP_A>(next, t, nxt);
     __builtin_amdgcn_sched_barrier(0);
     auto rest = [&](float2 (&x)[16]) {
-        fft_a(x, t, T, tw1);
+        if constexpr (CFO<ROT>)
+            fft_a_rot<true>(x, t, T, tw1, rot);
+        else
+            fft_a(x, t, T, tw1);
         __builtin_amdgcn_sched_barrier(0);
         if (PREF) row_load_part<PP_A, PP_A + PP_B>(next, t, nxt);
         __builtin_amdgcn_sched_barrier(0);
@@ -460,10 +438,11 @@ __device__ __forceinline__ void row0_dma(const float2 *sym, int t, float2 *T) {
     for (int j = 0; j < 8; ++j) dma16(src + j * 1024, dst + j * 1024);
 }
 
-template <bool SHARED, bool R0 = false, class IQ>
+template <bool SHARED, bool R0 = false, class IQ, class ROT = NoRot>
 __device__ __forceinline__ void hlds_rows(const IQ *sym, int Cp, int R, const float4 *Hf, int t,
                                           float2 *T, const float2 *tw1, const float2 *tw2,
-                                          float2 *T0, float4 *hfree, float2 (&acc)[16]) {
+                                          float2 *T0, float4 *hfree, float2 (&acc)[16], const ROT &rot = {}) {
+    static_assert(!CFO<ROT> || (R0 && !is_sc16<IQ>), "rotated rows: fp32 with row-0 DMA");
     using namespace hlds;
 #pragma unroll
     for (int k = 0; k < 16; ++k) acc[k] = float2{0.f, 0.f};
@@ -495,7 +474,7 @@ __device__ __forceinline__ void hlds_rows(const IQ *sym, int Cp, int R, const fl
             // prefetch
             auto row = [&](auto pref, int r, row_reg_t<IQ>(&cur)[16], row_reg_t<IQ>(&nxt)[16]) {
                 hlds_row_pp<decltype(pref)::value>(sym + (long long)(r + 1) * Cp, hc, r * (C * 8) + hw, lane_here(), cur,
-                                                   nxt, T, tw1, tw2, lo, hi, mine, acc);
+                                                   nxt, T, tw1, tw2, lo, hi, mine, acc, rot);
             };
             int r = 0;
             if ((R & 1) == 0) {
@@ -526,91 +505,10 @@ __device__ __forceinline__ void hlds_rows(const IQ *sym, int Cp, int R, const fl
             } else {
                 row_load<true>(sym + (long long)r * Cp, t, a);
             }
-            fft_a(a, t, T, tw1);
-            fft_b(t, T, tw2, x);
-            __builtin_amdgcn_sched_barrier(0);
-            hc_load(Hf + (long long)r * (C / 2), t, h);
-#pragma unroll
-            for (int k = 0; k < 16; ++k) mac(acc[k], x[k], h[k].x, h[k].y);
-        }
-    }
-}
-
-// The rows of k_mrc_td1024_hlds_cfo: hlds_row_pp / hlds_rows for fp32 rows with
-// the CFO rotation in (fft_a_rot), functions of their own so that the code
-// generation of the kernels without a rotation is not touched.  SHARED takes
-// tw1 with the lane factor folded in.
-template <bool PREF>
-__device__ __forceinline__ void hlds_row_pp_cfo(const float2 *next, __amdgpu_buffer_rsrc_t hc, int hoff, int t,
-                                                float2 (&cur)[16], float2 (&nxt)[16], float2 *T,
-                                                const float2 *tw1, const float2 *tw2, const float4 *lo,
-                                                const float4 *hi, float4 *mine, float2 (&acc)[16],
-                                                const Rot &rot) {
-    using namespace hlds;
-    const float4 hreg = __builtin_bit_cast(float4, (v4i_t)__builtin_amdgcn_raw_buffer_load_b128(hc, t * 16, hoff, 0));
-    if (PREF) row_load_part<0, PP_A>(next, t, nxt);
-    __builtin_amdgcn_sched_barrier(0);
-    fft_a_rot<true>(cur, t, T, tw1, rot);
-    __builtin_amdgcn_sched_barrier(0);
-    if (PREF) row_load_part<PP_A, PP_A + PP_B>(next, t, nxt);
-    __builtin_amdgcn_sched_barrier(0);
-    fft_b(t, T, tw2, cur);
-    __builtin_amdgcn_sched_barrier(0);
-    if (PREF) row_load_part<PP_A + PP_B, PP_A + PP_B + PP_C>(next, t, nxt);
-    __builtin_amdgcn_sched_barrier(0);
-    lds_barrier();  // every wave is done with the previous Hc row
-    *mine = hreg;
-    lds_barrier();
-    if (PREF) row_load_part<PP_A + PP_B + PP_C, 16>(next, t, nxt);
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const float4 v = i < 4 ? lo[i * 64] : hi[(i - 4) * TS];  // 2 images = TS float4s
-        mac(acc[2 * i], cur[2 * i], v.x, v.y);
-        mac(acc[2 * i + 1], cur[2 * i + 1], v.z, v.w);
-    }
-}
-template <bool SHARED>
-__device__ __forceinline__ void hlds_rows_cfo(const float2 *sym, int Cp, int R, const float4 *Hf, int t, float2 *T,
-                                              const float2 *tw1, const float2 *tw2, float2 *T0, float4 *hfree,
-                                              float2 (&acc)[16], const Rot &rot) {
-    using namespace hlds;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) acc[k] = float2{0.f, 0.f};
-    if constexpr (SHARED) {
-        float2 a[16], b[16];
-        const int tl = lane_here();
-        const float4 *lo = hfree + tl;
-        const float4 *hi = hslot(T0, hfree, 256 + tl);
-        float4 *mine = hslot(T0, hfree, threadIdx.x);
-        const __amdgpu_buffer_rsrc_t hc =
-            __builtin_amdgcn_make_buffer_rsrc(const_cast<float4 *>(Hf), (short)0, R * (C * 8), 0x00020000);
-        const int hw = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) * 1024;
-        auto row = [&](auto pref, int r, float2(&cur)[16], float2(&nxt)[16]) {
-            hlds_row_pp_cfo<decltype(pref)::value>(sym + (long long)(r + 1) * Cp, hc, r * (C * 8) + hw, lane_here(),
-                                                   cur, nxt, T, tw1, tw2, lo, hi, mine, acc, rot);
-        };
-        int r = 0;
-        if ((R & 1) == 0) {
-            row0<true>(sym, tl, T, b);
-            row(std::true_type{}, 0, b, a);
-            r = 1;
-        } else {
-            row0<true>(sym, tl, T, a);
-        }
-        for (; r + 2 < R; r += 2) {
-            row(std::true_type{}, r, a, b);
-            row(std::true_type{}, r + 1, b, a);
-        }
-        row(std::false_type{}, r, a, b);
-    } else {
-        for (int r = 0; r < R; ++r) {
-            float2 a[16], x[16], h[16];
-            if (r == 0)
-                row0<true>(sym, t, T, a);
+            if constexpr (CFO<ROT>)
+                fft_a_rot<false>(a, t, T, tw1, rot);
             else
-                row_load<true>(sym + (long long)r * Cp, t, a);
-            fft_a_rot<false>(a, t, T, tw1, rot);
+                fft_a(a, t, T, tw1);
             fft_b(t, T, tw2, x);
             __builtin_amdgcn_sched_barrier(0);
             hc_load(Hf + (long long)r * (C / 2), t, h);
@@ -677,12 +575,15 @@ __device__ __forceinline__ void hlds_epilogue(const float2 (&acc)[16], const flo
 // (blocks b and b+8 share an XCD under round-robin dispatch, so a frame's
 // workgroups share its Hc rows in one L2; speed only, never correctness).
 // mode 0: out[q][out_pos(j)] = acc / P;  mode 1: out[q][j] = acc (numerator).
-// IQ = sc16: `scale` (ignored for float2) turns the raw integers into samples.
-template <bool R0, class IQ>
+// IQ = sc16: `last` is the scale (ignored for float2) that turns the raw
+// integers into samples.  SRC = src_cfo: `last` is eps, the rows are those of
+// x' and the estimate is that of x'.
+template <bool R0, class IQ, class SRC>
 __global__ void __attribute__((amdgpu_flat_work_group_size(512, 512), amdgpu_waves_per_eu(4, 4)))
 k_mrc_td1024_hlds(const IQ *__restrict__ iq, int S, int R, int prefix, const float2 *__restrict__ Hc,
                   const float *__restrict__ P, float2 *__restrict__ out, long long nq, long long nblocks,
-                  long long per_xcd, int mode, float scale) {
+                  long long per_xcd, int mode, typename SRC::arg last) {
+    static_assert(!CFO<SRC> || (R0 && !is_sc16<IQ>), "the CFO policy covers fp32 rows with row-0 DMA");
     using namespace hlds;
     constexpr int HW = WAVES;
     extern __shared__ __attribute__((aligned(16))) float2 lds[];
@@ -711,82 +612,39 @@ k_mrc_td1024_hlds(const IQ *__restrict__ iq, int S, int R, int prefix, const flo
     const IQ *sym = iq + (f * S + s) * (long long)R * Cp + prefix;
     if constexpr (R0) row0_dma(sym, t, T);
     fill(tw1, tw2);
-    __syncthreads();
-
-    float2 acc[16];
-    if (f0 == fl)
-        hlds_rows<true, R0>(sym, Cp, R, reinterpret_cast<const float4 *>(Hc + f0 * (long long)R * C), t, T,
-                                 tw1, tw2, T0, hfree, acc);
-    else
-        hlds_rows<false, R0>(sym, Cp, R, reinterpret_cast<const float4 *>(Hc + f * (long long)R * C), t, T,
-                                tw1, tw2, T0, hfree, acc);
-    if (!store) return;
-    if constexpr (is_sc16<IQ>)
-        hlds_epilogue<true>(acc, P, f, q, lane_here(), T, out, mode, scale);
-    else
-        hlds_epilogue(acc, P, f, q, lane_here(), T, out, mode);
-}
-
-
-// k_mrc_td1024_hlds<true, float2> on x' (eps: one offset per frame) against the
-// estimate of x': the same body with the rotation in -- a kernel of its own,
-// so that the others' code generation is not touched.
-__global__ void __attribute__((amdgpu_flat_work_group_size(512, 512), amdgpu_waves_per_eu(4, 4)))
-k_mrc_td1024_hlds_cfo(const float2 *__restrict__ iq, int S, int R, int prefix, const float2 *__restrict__ Hc,
-                      const float *__restrict__ P, float2 *__restrict__ out, long long nq, long long nblocks,
-                      long long per_xcd, int mode, const float *__restrict__ eps) {
-    constexpr bool R0 = true;  // row 0 by LDS-DMA, as the fp32 kernel
-    using namespace hlds;
-    constexpr int HW = WAVES;
-    extern __shared__ __attribute__((aligned(16))) float2 lds[];
-    float2 *tw1 = lds, *tw2 = lds + TW1S;
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), t = threadIdx.x & 63;
-    float2 *T = lds + TW1S + TW2S + w * TS;
-    float2 *T0 = lds + TW1S + TW2S;
-    float4 *hfree = reinterpret_cast<float4 *>(T0 + HW * TS);
-    const long long pb = blockIdx.x;
-    const long long lb = (pb & 7) * per_xcd + (pb >> 3);  // XCD-grouped logical block
-    if (lb >= nblocks) return;
-
-    // every wave takes part in the per-row barriers: tail waves duplicate the
-    // last symbol and do not store
-    const int nsym = S - 1;
-    const long long qw = lb * HW + w;
-    const bool store = qw < nq;
-    const long long q = store ? qw : nq - 1;
-    // the workgroup's Hc rows come from the frame of its first symbol; a
-    // workgroup straddling two frames falls back to per-wave L2 loads
-    const long long f = uniform64(q / nsym);  // wave-uniform: SGPRs across the row loop
-    const long long f0 = (lb * HW) / nsym;
-    const long long fl = ((lb * HW + HW - 1 < nq ? lb * HW + HW - 1 : nq - 1)) / nsym;
-    const int s = 1 + (int)(q % nsym);
-    const int Cp = C + prefix;
-    const float2 *sym = iq + (f * S + s) * (long long)R * Cp + prefix;
-    if constexpr (R0) row0_dma(sym, t, T);
-    fill(tw1, tw2);
-    // this wave's frame: every wave of a workgroup inside one frame has the same
-    // offset, and each thread folds its lane factor into the table entries it
-    // has just written itself (fill: i = threadIdx.x, + 512; i % 64 = t)
-    const float e = uniform_f(cfo_eps(eps, f));
-    const Rot rot = make_rot(e, t);
-    if (f0 == fl) {
-        for (int i = threadIdx.x; i < TW1S; i += blockDim.x) tw1[i] = cmul(tw1[i], rot.l);
+    [[maybe_unused]] float e;
+    typename SRC::rot rot;
+    if constexpr (CFO<SRC>) {
+        // this wave's frame: every wave of a workgroup inside one frame has the
+        // same offset, and each thread folds its lane factor into the table
+        // entries it has just written itself (fill: i = threadIdx.x, + 512;
+        // i % 64 = t)
+        e = uniform_f(cfo_eps(last, f));
+        rot = make_rot(e, t);
+        if (f0 == fl) {
+            for (int i = threadIdx.x; i < TW1S; i += blockDim.x) tw1[i] = cmul(tw1[i], rot.l);
+        }
     }
     __syncthreads();
 
     float2 acc[16];
     if (f0 == fl)
-        hlds_rows_cfo<true>(sym, Cp, R, reinterpret_cast<const float4 *>(Hc + f0 * (long long)R * C), t, T, tw1,
-                            tw2, T0, hfree, acc, rot);
+        hlds_rows<true, R0>(sym, Cp, R, reinterpret_cast<const float4 *>(Hc + f0 * (long long)R * C), t, T,
+                                 tw1, tw2, T0, hfree, acc, rot);
     else
-        hlds_rows_cfo<false>(sym, Cp, R, reinterpret_cast<const float4 *>(Hc + f * (long long)R * C), t, T, tw1,
-                             tw2, T0, hfree, acc, rot);
+        hlds_rows<false, R0>(sym, Cp, R, reinterpret_cast<const float4 *>(Hc + f * (long long)R * C), t, T,
+                                tw1, tw2, T0, hfree, acc, rot);
     if (!store) return;
-    // the symbol's start phase, once per output
-    const float2 ps = cfo_symbol_phase(e, (long long)s * Cp + prefix, -1.f);
+    if constexpr (CFO<SRC>) {
+        // the symbol's start phase, once per output
+        const float2 ps = cfo_symbol_phase(e, (long long)s * Cp + prefix, -1.f);
 #pragma unroll
-    for (int k = 0; k < 16; ++k) acc[k] = cmul(acc[k], ps);
-    hlds_epilogue(acc, P, f, q, lane_here(), T, out, mode);
+        for (int k = 0; k < 16; ++k) acc[k] = cmul(acc[k], ps);
+    }
+    if constexpr (is_sc16<IQ>)
+        hlds_epilogue<true>(acc, P, f, q, lane_here(), T, out, mode, last);
+    else
+        hlds_epilogue(acc, P, f, q, lane_here(), T, out, mode);
 }
 
 
@@ -1040,56 +898,32 @@ k_demod_td1024(const float2 *__restrict__ iq, int S, int R, int prefix, const fl
 }  // namespace td1024
 
 namespace {
-// eps != null: the CFO kernels (fp32 only; their last argument is eps where
-// the others take the sc16 scale)
-template <class IQ>
-hipError_t ls_td1024(const IQ *iq, long long nframes, int S, int R, int prefix, float scale,
-                     const float2 *X, float2 *Hc, float *P, int partial, hipStream_t s,
-                     const float *eps = nullptr) {
+// `last`: the kernels' last argument under SRC (the sc16 scale, or eps)
+template <class SRC, class IQ>
+hipError_t ls_td1024(const IQ *iq, long long nframes, int S, int R, int prefix, typename SRC::arg last,
+                     const float2 *X, float2 *Hc, float *P, int partial, hipStream_t s) {
     using namespace td1024;
     if (nframes <= 0) return hipSuccess;
     if (nframes > 0x7fffffffll) return hipErrorInvalidValue;
     // 4-wave workgroups unless they leave the GPU under-filled: fewer than
     // 2 waves per SIMD (2048 waves) with rows left to spread
-    int nw = (nframes * LS_WAVES < 2048 && R > LS_WAVES) ? 16 : LS_WAVES;
-    if constexpr (!is_sc16<IQ>) {
-        if (eps) {
-            if (nw == 16) {
-                const size_t lds = (TWBUF + 16 * TBUF) * sizeof(float2);
-                if (hipError_t e = opt_in_lds(reinterpret_cast<const void *>(k_ls_td1024_cfo<16>), (int)lds);
-                    e != hipSuccess)
-                    return e;
-                hipLaunchKernelGGL(k_ls_td1024_cfo<16>, dim3((unsigned)nframes), dim3(64 * 16), lds, s, iq, S, R,
-                                   prefix, X, Hc, P, partial, eps);
-            } else {
-                const size_t lds = (TWBUF + LS_WAVES * TBUF) * sizeof(float2);
-                hipLaunchKernelGGL(k_ls_td1024_cfo<LS_WAVES>, dim3((unsigned)nframes), dim3(64 * LS_WAVES), lds, s,
-                                   iq, S, R, prefix, X, Hc, P, partial, eps);
-            }
-            return hipGetLastError();
-        }
-    }
-    auto k16 = k_ls_td1024<16, IQ>;
-    auto k4 = k_ls_td1024<LS_WAVES, IQ>;
-    auto k8 = k16;  // 8-wave workgroups: A/B build only
-    if (nw == 16 || nw == 8) {
-        auto kern = nw == 16 ? k16 : k8;
-        const size_t lds = (TWBUF + nw * TBUF) * sizeof(float2);
-        if (hipError_t e = opt_in_lds(reinterpret_cast<const void *>(kern), (int)lds); e != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, dim3((unsigned)nframes), dim3(64 * nw), lds, s, iq, S, R, prefix, X, Hc, P,
-                           partial, scale);
+    if (nframes * LS_WAVES < 2048 && R > LS_WAVES) {
+        auto k16 = k_ls_td1024<16, IQ, SRC>;
+        const size_t lds = (TWBUF + 16 * TBUF) * sizeof(float2);
+        if (hipError_t e = opt_in_lds(reinterpret_cast<const void *>(k16), (int)lds); e != hipSuccess) return e;
+        hipLaunchKernelGGL(k16, dim3((unsigned)nframes), dim3(64 * 16), lds, s, iq, S, R, prefix, X, Hc, P, partial,
+                           last);
         return hipGetLastError();
     }
     const size_t lds = (TWBUF + LS_WAVES * TBUF) * sizeof(float2);
-    hipLaunchKernelGGL(k4, dim3((unsigned)nframes), dim3(64 * LS_WAVES), lds, s, iq, S, R, prefix, X, Hc, P,
-                       partial, scale);
+    hipLaunchKernelGGL((k_ls_td1024<LS_WAVES, IQ, SRC>), dim3((unsigned)nframes), dim3(64 * LS_WAVES), lds, s, iq, S,
+                       R, prefix, X, Hc, P, partial, last);
     return hipGetLastError();
 }
 
-template <class IQ>
-hipError_t mrc_td1024(const IQ *iq, long long nframes, int S, int R, int prefix, float scale,
-                      const float2 *Hc, const float *P, float2 *out, int mode, hipStream_t s,
-                      const float *eps = nullptr) {
+template <class SRC, class IQ>
+hipError_t mrc_td1024(const IQ *iq, long long nframes, int S, int R, int prefix, typename SRC::arg last,
+                      const float2 *Hc, const float *P, float2 *out, int mode, hipStream_t s) {
     using namespace td1024;
     const long long nq = nframes * (S - 1);
     if (nq <= 0) return hipSuccess;
@@ -1103,44 +937,26 @@ hipError_t mrc_td1024(const IQ *iq, long long nframes, int S, int R, int prefix,
     // without scratch (profiles/r6/r6m2_*).
     // sc16 rows are only 4-byte aligned (any cp_len): their row 0 comes by
     // naturally aligned dword loads like every other row, not by 16-B DMA.
-    if constexpr (!is_sc16<IQ>) {
-        if (eps) {
-            hipLaunchKernelGGL(k_mrc_td1024_hlds_cfo, dim3((unsigned)(pxcd * 8)), dim3(64 * hlds::WAVES),
-                               hlds::LDS_BYTES, s, iq, S, R, prefix, Hc, P, out, nq, nb, pxcd, mode, eps);
-            return hipGetLastError();
-        }
-    }
-    auto kern = k_mrc_td1024_hlds<!is_sc16<IQ>, IQ>;
+    auto kern = k_mrc_td1024_hlds<!is_sc16<IQ>, IQ, SRC>;
     hipLaunchKernelGGL(kern, dim3((unsigned)(pxcd * 8)), dim3(64 * hlds::WAVES), hlds::LDS_BYTES, s, iq, S, R,
-                       prefix, Hc, P, out, nq, nb, pxcd, mode, scale);
+                       prefix, Hc, P, out, nq, nb, pxcd, mode, last);
     return hipGetLastError();
 }
 }  // namespace
 
-hipError_t launch_ls_td1024(const float2 *iq, long long nframes, int S, int R, int prefix,
-                            const float2 *X, float2 *Hc, float *P, int partial, hipStream_t s) {
-    return ls_td1024(iq, nframes, S, R, prefix, 1.f, X, Hc, P, partial, s);
+hipError_t launch_ls_td1024(const Iq1024 &src, long long nframes, int S, int R, int prefix, const float2 *X,
+                            float2 *Hc, float *P, int partial, hipStream_t s) {
+    using namespace td1024;
+    if (src.i16) return ls_td1024<src_plain>(src.i16, nframes, S, R, prefix, src.scale, X, Hc, P, partial, s);
+    if (src.eps) return ls_td1024<src_cfo>(src.f32, nframes, S, R, prefix, src.eps, X, Hc, P, partial, s);
+    return ls_td1024<src_plain>(src.f32, nframes, S, R, prefix, 1.f, X, Hc, P, partial, s);
 }
-hipError_t launch_ls_td1024_sc16(const sc16 *iq, long long nframes, int S, int R, int prefix, float scale,
-                                 const float2 *X, float2 *Hc, float *P, int partial, hipStream_t s) {
-    return ls_td1024(iq, nframes, S, R, prefix, scale, X, Hc, P, partial, s);
-}
-hipError_t launch_mrc_td1024(const float2 *iq, long long nframes, int S, int R, int prefix,
-                             const float2 *Hc, const float *P, float2 *out, int mode,
-                             hipStream_t s) {
-    return mrc_td1024(iq, nframes, S, R, prefix, 1.f, Hc, P, out, mode, s);
-}
-hipError_t launch_mrc_td1024_sc16(const sc16 *iq, long long nframes, int S, int R, int prefix, float scale,
-                                  const float2 *Hc, const float *P, float2 *out, int mode, hipStream_t s) {
-    return mrc_td1024(iq, nframes, S, R, prefix, scale, Hc, P, out, mode, s);
-}
-hipError_t launch_ls_td1024_cfo(const float2 *iq, long long nframes, int S, int R, int prefix, const float *eps,
-                                const float2 *X, float2 *Hc, float *P, hipStream_t s) {
-    return ls_td1024(iq, nframes, S, R, prefix, 1.f, X, Hc, P, 0, s, eps);
-}
-hipError_t launch_mrc_td1024_cfo(const float2 *iq, long long nframes, int S, int R, int prefix, const float *eps,
-                                 const float2 *Hc, const float *P, float2 *out, hipStream_t s) {
-    return mrc_td1024(iq, nframes, S, R, prefix, 1.f, Hc, P, out, 0, s, eps);
+hipError_t launch_mrc_td1024(const Iq1024 &src, long long nframes, int S, int R, int prefix, const float2 *Hc,
+                             const float *P, float2 *out, int mode, hipStream_t s) {
+    using namespace td1024;
+    if (src.i16) return mrc_td1024<src_plain>(src.i16, nframes, S, R, prefix, src.scale, Hc, P, out, mode, s);
+    if (src.eps) return mrc_td1024<src_cfo>(src.f32, nframes, S, R, prefix, src.eps, Hc, P, out, mode, s);
+    return mrc_td1024<src_plain>(src.f32, nframes, S, R, prefix, 1.f, Hc, P, out, mode, s);
 }
 
 // One-launch LS + MRC (ofdm_frame_demod, mode 0).  flags: nframes 64-bit

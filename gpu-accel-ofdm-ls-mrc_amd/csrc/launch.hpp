@@ -116,15 +116,34 @@ hipError_t launch_mrc_freq_mfma(const float2 *Y, long long frame_stride, long lo
 hipError_t launch_mrc_finalize(const float2 *num, long long e0, long long count, int nsym,
                                int K, const float *P, float2 *out, hipStream_t s);
 
-// Fused time-domain receiver, C = 1024 (32 x 32 wave FFT).
-// Frames: iq + f*S*R*(C+prefix); pilot = symbol 0, data = symbols 1..S-1.
-// Workspace: Hc [F][R][C] (bin layout), P [F][C].
-hipError_t launch_ls_td1024(const float2 *iq, long long nframes, int S, int R, int prefix,
-                            const float2 *X, float2 *Hc, float *P, int partial,
-                            hipStream_t s);
-hipError_t launch_mrc_td1024(const float2 *iq, long long nframes, int S, int R, int prefix,
-                             const float2 *Hc, const float *P, float2 *out, int mode,
-                             hipStream_t s);
+// One sc16 sample as the radio puts it on the wire (ofdm_sc16: int16 re in
+// the low half of the little-endian dword, int16 im in the high half).
+struct sc16 {
+    unsigned v;
+};
+// The sample source of the two-launch C = 1024 receiver: fp32 frames (f32), or
+// sc16 frames (i16: x = (float)i16 * scale; rows need 4-byte alignment only),
+// exactly one of the two non-null.  eps (fp32 frames only, may be null): one
+// carrier frequency offset per frame, in subcarrier spacings; the kernels then
+// receive the derotated frames (cfo.hip states the convention).
+struct Iq1024 {
+    const float2 *f32;
+    const sc16 *i16;
+    float scale;
+    const float *eps;
+};
+inline Iq1024 iq_f32(const float2 *iq, const float *eps = nullptr) { return {iq, nullptr, 1.f, eps}; }
+inline Iq1024 iq_sc16(const sc16 *iq, float scale) { return {nullptr, iq, scale, nullptr}; }
+
+// Fused time-domain receiver, C = 1024 (32 x 32 wave FFT), the same kernels
+// instantiated on the sample source.
+// Frames: src + f*S*R*(C+prefix); pilot = symbol 0, data = symbols 1..S-1.
+// Workspace: Hc [F][R][C] (bin layout), P [F][C], in the units of x whatever
+// the source, so a workspace serves any source's MRC.
+hipError_t launch_ls_td1024(const Iq1024 &src, long long nframes, int S, int R, int prefix, const float2 *X,
+                            float2 *Hc, float *P, int partial, hipStream_t s);
+hipError_t launch_mrc_td1024(const Iq1024 &src, long long nframes, int S, int R, int prefix, const float2 *Hc,
+                             const float *P, float2 *out, int mode, hipStream_t s);
 // Both in one grid (frame_td.hip k_demod_td1024): estimator workgroups
 // publish each frame's estimate through flags[f] = epoch (agent scope), the
 // MRC workgroups wait for it.  flags: nframes words in the workspace; epoch:
@@ -134,19 +153,6 @@ hipError_t launch_demod_td1024(const float2 *iq, long long nframes, int S, int R
                                unsigned long long *flags, unsigned long long epoch, long long spin_ticks,
                                hipStream_t s);
 
-// One sc16 sample as the radio puts it on the wire (ofdm_sc16: int16 re in
-// the low half of the little-endian dword, int16 im in the high half).
-struct sc16 {
-    unsigned v;
-};
-// The two-launch C = 1024 receiver on sc16 frames (the same kernels,
-// instantiated on the sample type): the fp32 launchers' contracts applied to
-// x = (float)i16 * scale.  Hc and P come out in true units, so a workspace
-// serves either format's MRC.  Rows need 4-byte alignment only.
-hipError_t launch_ls_td1024_sc16(const sc16 *iq, long long nframes, int S, int R, int prefix, float scale,
-                                 const float2 *X, float2 *Hc, float *P, int partial, hipStream_t s);
-hipError_t launch_mrc_td1024_sc16(const sc16 *iq, long long nframes, int S, int R, int prefix, float scale,
-                                  const float2 *Hc, const float *P, float2 *out, int mode, hipStream_t s);
 // out[i] = {float(re) * scale, float(im) * scale}, i < n (iq_sc16.hip); in
 // and out 16-B aligned.
 hipError_t launch_iq_sc16_to_cf32(const sc16 *in, long long n, float scale, float2 *out, hipStream_t s);
@@ -155,17 +161,12 @@ hipError_t launch_iq_sc16_to_cf32(const sc16 *in, long long n, float scale, floa
 // frame, in subcarrier spacings).  cfo_estimate: gamma[f] (may be null) and
 // eps[f] = arg(gamma[f]) / 2 pi from the cyclic prefixes of frame f, samples
 // cp_skip .. cp-1 of every row; any C.  cfo_derotate: out = in e^{-2 pi i eps m
-// / C} over whole rows, out == in or disjoint.  The _cfo launchers: the
-// two-launch C = 1024 receiver (frame_td.hip) on the derotated frames, full
-// demod (mode 0, no antenna split).
+// / C} over whole rows, out == in or disjoint.  The C = 1024 receiver on the
+// derotated frames: launch_{ls,mrc}_td1024 with Iq1024::eps.
 hipError_t launch_cfo_estimate(const float2 *iq, long long nframes, int S, int R, int C, int cp, int cp_skip,
                                float2 *gamma, float *eps, hipStream_t s);
 hipError_t launch_cfo_derotate(const float2 *in, float2 *out, long long nframes, int S, int R, int C, int cp,
                                const float *eps, hipStream_t s);
-hipError_t launch_ls_td1024_cfo(const float2 *iq, long long nframes, int S, int R, int prefix, const float *eps,
-                                const float2 *X, float2 *Hc, float *P, hipStream_t s);
-hipError_t launch_mrc_td1024_cfo(const float2 *iq, long long nframes, int S, int R, int prefix, const float *eps,
-                                 const float2 *Hc, const float *P, float2 *out, hipStream_t s);
 
 // Stage-wise operations of the reference's per-stage gpuLS methods (stages.hip).
 // fused time-domain receiver, C = 2048 (frame_td2048.hip); same contracts
