@@ -266,7 +266,10 @@ size_t zf_precoder_lds_bytes(int U, int R);
 hipError_t launch_zf_precoder(const float2 *Hin, int U, int R, int K, float2 *W, float2 *Wt,
                               hipStream_t s);
 hipError_t launch_zf_transpose(const float2 *W, int U, int R, int K, float2 *Wt, hipStream_t s);
-// apply: Y[s][r][k] = sum_u W(r,u) X[s][u][k]; detect: X[s][u][k] = sum_r conj(W(r,u)) Y[s][r][k]
+// apply: Y[s][r][k] = sum_u W(r,u) X[s][u][k]; detect: X[s][u][k] = sum_r conj(W(r,u)) Y[s][r][k].
+// The kernel follows from (U, R, K) alone.  Apply: the 16-B-lane W-stationary kernel for K >= 2 and
+// R >= 8, else register tiles (fed through LDS for 5 <= R < 8 with U >= 8).  Detect: register tiles for R < 8 or U <= 8, the W-stationary MFMA
+// kernel for R <= 72, else the LDS-fed MFMA kernels.  A grid past 2^31 - 1 blocks: hipErrorInvalidValue.
 hipError_t launch_zf_apply(const float2 *Wt, const float2 *X, int U, int R, int K, long long nsym,
                            float2 *Y, hipStream_t s);
 hipError_t launch_zf_detect(const float2 *Wt, const float2 *Y, int U, int R, int K, long long nsym,

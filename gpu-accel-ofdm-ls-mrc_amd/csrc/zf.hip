@@ -15,22 +15,28 @@
 //     the reference's layout W[k][u][r] (per subcarrier R x U column-major)
 //     and/or the subcarrier-fastest layout Wt[u][r][k] the apply / detect
 //     kernels read with coalesced loads.
-//   k_zf_gemm: the symbol-batched application -- for every subcarrier a small
-//     complex GEMM out_k (M x nsym) = A_k (M x N) . in_k (N x nsym), A_k = W
-//     (apply: M = R, N = U) or W^H (detect: M = U, N = R).  Lanes = 64
-//     consecutive subcarriers (the fastest axis of every operand, so each load
-//     and store is one coalesced 512 B wave access); each wave accumulates an
-//     MT x ST (rows x symbols) register tile, so per n it loads MT + ST values
-//     for MT * ST complex MACs.  At U = 16, R = 64 the work is ~13 flop per HBM
-//     byte, under the FP32 ridge (~20): HBM-bound on paper (at U = 32, 26
-//     flop/B, compute-bound).  The f32 matrix peak of gfx950 equals its f32
-//     vector peak (MI355X_MICROARCH.md); the k_zf_mfma_* / k_zf_wstat kernels
-//     below put the MACs on the matrix cores anyway (16-block 4x4x1 MFMA, one
-//     block per subcarrier) and win for detect at U > 8.
-//     The W tile of a (subcarrier block, row block) is re-read for every symbol
-//     step; block ids are mapped so that all workgroups of one XCD share the
-//     same few tiles (dispatch is round-robin over the 8 XCDs), keeping those
-//     re-reads in that XCD's 4 MB L2 instead of HBM.
+//   The symbol-batched application is, for every subcarrier, a small complex
+//   GEMM out_k (M x nsym) = A_k (M x N) . in_k (N x nsym), A_k = W (apply:
+//   M = R, N = U) or W^H (detect: M = U, N = R).  At U = 16, R = 64 the work
+//   is ~13 flop per HBM byte, under the FP32 ridge (~20): HBM-bound on paper
+//   (at U = 32, 26 flop/B, compute-bound).  Six kernels, chosen by shape
+//   alone (the table above launch_zf_apply, end of this file):
+//   k_zf_gemm: lanes = 64 consecutive subcarriers (the fastest axis of every
+//     operand, so each load and store is one coalesced 512 B wave access);
+//     each wave accumulates an MT x 8 (rows x symbols) register tile, so per
+//     n it loads MT + 8 values for 8 MT complex MACs.  The W tile of a
+//     (subcarrier block, row block) is re-read for every symbol step; block
+//     ids are mapped so that all workgroups of one XCD share the same few
+//     tiles (dispatch is round-robin over the 8 XCDs), keeping those re-reads
+//     in that XCD's 4 MB L2 instead of HBM.  Detect at U <= 8 and every shape
+//     the kernels below do not take (R < 8, K = 1).
+//   k_zf_gemm_lds: the same tiles fed through LDS, for the apply with 5 to 7
+//     antennas and 8 or more users.
+//   k_zf_wstat, k_zf_mfma_lds8, k_zf_mfma_w128: detect at U > 8 on the matrix
+//     cores (16-block 4x4x1 MFMA, one block per subcarrier).  The f32 matrix
+//     peak of gfx950 equals its f32 vector peak (MI355X_MICROARCH.md); they
+//     win by how they feed the operands, not by the MAC rate.
+//   k_zf_apply_ws16: the apply with two subcarriers (16 B) per lane.
 #include <hip/hip_runtime.h>
 
 #include "launch.hpp"
@@ -212,15 +218,15 @@ __global__ void __launch_bounds__(256) k_zf_transpose(const float2 *__restrict__
 // A_k(m, n) = Wt[(m*a_m + n*a_n)*K + k] (conjugated if CONJ).
 // Workgroup = 4 waves = MG row groups x (4/MG) symbol groups; it owns the
 // rows [mb*MG*MT, +MG*MT) of a 64-subcarrier block and walks its symbol chunk
-// in steps of (4/MG)*ST symbols.
-// PF: the loads of step n+1 are issued before the MACs of step n (register
-// double buffering), so a wave's memory latency overlaps its own arithmetic.
-template <int MT, int ST, int MG, bool CONJ, bool PF>
+// in steps of (4/MG)*ST symbols, ST = 8 per wave.  The loads of step n+1 are
+// issued before the MACs of step n (register double buffering), so a wave's
+// memory latency overlaps its own arithmetic.
+template <int MT, int MG, bool CONJ>
 __global__ void __launch_bounds__(256) k_zf_gemm(const float2 *__restrict__ Wt, int a_m, int a_n,
                                                  const float2 *__restrict__ in, int N, int M, int K,
                                                  long long nsym, float2 *__restrict__ out, int ntile,
                                                  int tpx, int nkb, long long chunk_steps) {
-    constexpr int SG = 4 / MG, SBLK = SG * ST;
+    constexpr int ST = 8, SG = 4 / MG, SBLK = SG * ST;
     // XCD-aware block mapping: block b runs on XCD b % 8; XCD x owns tiles
     // x, x+8, x+16, ... and walks all symbol chunks of them.
     const int b = blockIdx.x, xcd = b & 7, j = b >> 3;
@@ -260,14 +266,11 @@ __global__ void __launch_bounds__(256) k_zf_gemm(const float2 *__restrict__ Wt, 
 #pragma unroll
             for (int jj = 0; jj < ST; ++jj) xv[jj] = xn[min(jj, slast) * NK];
         };
-        if (PF) load(0, a, x);
+        load(0, a, x);
 #pragma unroll 2
         for (int n = 0; n < N; ++n) {
             float2 an[MT], xnx[ST];
-            if (PF)
-                load(min(n + 1, N - 1), an, xnx);  // the last one is a redundant reload
-            else
-                load(n, a, x);
+            load(min(n + 1, N - 1), an, xnx);  // the last one is a redundant reload
             // complex MAC as 4 FMAs straight into the accumulator
 #pragma unroll
             for (int i = 0; i < MT; ++i) {
@@ -278,12 +281,10 @@ __global__ void __launch_bounds__(256) k_zf_gemm(const float2 *__restrict__ Wt, 
                     acc[i][jj].y = fmaf(ar, x[jj].y, fmaf(ai, x[jj].x, acc[i][jj].y));
                 }
             }
-            if (PF) {
 #pragma unroll
-                for (int i = 0; i < MT; ++i) a[i] = an[i];
+            for (int i = 0; i < MT; ++i) a[i] = an[i];
 #pragma unroll
-                for (int jj = 0; jj < ST; ++jj) x[jj] = xnx[jj];
-            }
+            for (int jj = 0; jj < ST; ++jj) x[jj] = xnx[jj];
         }
 #pragma unroll
         for (int jj = 0; jj < ST; ++jj) {
@@ -296,32 +297,28 @@ __global__ void __launch_bounds__(256) k_zf_gemm(const float2 *__restrict__ Wt, 
     }
 }
 
-// The same GEMM with the operand tiles shared through LDS (default for M > 4,
-// N >= 8).
-// Each wave of k_zf_gemm loads its own 8 + 8 operand rows per n, so at U = 16
-// the per-CU L1 path (64 B/clk) had to carry twice the unique bytes and capped
-// the kernel at ~37 % of HBM.  Here the workgroup stages each chunk of NC
-// n-steps -- the MB = MG*8 rows of A and the SB = (4/MG)*8 symbols of the
-// input, 64 subcarriers each -- once, with plain coalesced loads into
-// registers, and every wave reads its 8 + 8 rows per n from LDS (128 B/clk,
-// conflict free: 64 lanes x 8 B contiguous).  The loads of chunk c+1 are in
-// flight while chunk c is computed; two LDS buffers, one barrier per chunk.
-// ST = 4, NC = 1 (OFDM_ZF_ST=4): 8x4 tiles, 64 accumulator VGPRs, 4 waves/SIMD.
-// XMAP (OFDM_ZF_XMAP=1): XCD x takes symbol chunks x, x + 8, ... with all
-// tiles (the k_zf_wstat map) instead of tiles x, x + 8, ... with all chunks.
-template <int MG, bool CONJ, bool NTIN = false, int ST = 8, int NC = 2, bool XMAP = false>
-__global__ void __attribute__((amdgpu_flat_work_group_size(256, 256), amdgpu_waves_per_eu(ST == 4 ? 4 : 1)))
+// The GEMM of k_zf_gemm for one 8-row tile of A = W (the apply at R < 8), with
+// the operand tiles shared through LDS.
+// Each wave of k_zf_gemm loads its own 8 + 8 operand rows per n through the
+// per-CU L1 path (64 B/clk).  Here the workgroup stages each chunk of NC = 2
+// n-steps -- the MB = 8 rows of A and the SB = 32 symbols of the input, 64
+// subcarriers each -- once, with plain coalesced loads into registers, and
+// every wave reads its 8 + 8 rows per n from LDS (128 B/clk, conflict free:
+// 64 lanes x 8 B contiguous).  The loads of chunk c+1 are in flight while
+// chunk c is computed; two LDS buffers, one barrier per chunk.
+__global__ void __attribute__((amdgpu_flat_work_group_size(256, 256), amdgpu_waves_per_eu(1)))
 k_zf_gemm_lds(const float2 *__restrict__ Wt, int a_m, int a_n, const float2 *__restrict__ in, int N, int M,
               int K, long long nsym, float2 *__restrict__ out, int ntile, int tpx, int nkb,
               long long chunk_steps) {
-    constexpr int MT = 8, SG = 4 / MG, MB = MG * MT, SB = SG * ST;
+    // MG = 1 row group of MT rows: the 4 waves are SG = 4 symbol groups of ST symbols
+    constexpr int MT = 8, ST = 8, NC = 2, MG = 1, SG = 4 / MG, MB = MG * MT, SB = SG * ST;
     constexpr int AROWS = NC * MB, ROWS = NC * (MB + SB), RPT = ROWS / 4, AI = AROWS / 4;
     static_assert(AROWS % 4 == 0 && ROWS % 4 == 0, "rows split evenly over the 4 waves");
     __shared__ float2 sm[2][ROWS * 64];
     const int b = blockIdx.x, xcd = b & 7, j = b >> 3;  // XCD-aware mapping as k_zf_gemm
-    const int tile = XMAP ? j % ntile : xcd + 8 * (j % tpx);
+    const int tile = xcd + 8 * (j % tpx);
     if (tile >= ntile) return;  // whole workgroup
-    const long long chunk = XMAP ? xcd + 8LL * (j / ntile) : j / tpx;
+    const long long chunk = j / tpx;
     const int kb = tile % nkb, mb = tile / nkb;
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -356,14 +353,10 @@ k_zf_gemm_lds(const float2 *__restrict__ Wt, int a_m, int a_n, const float2 *__r
             const float2 *px = in + (s0 * N + n0) * (long long)K + kc;
 #pragma unroll
             for (int i = 0; i < RPT; ++i) {
-                if (i < AI) {
+                if (i < AI)
                     stg[i] = pa[roff[i]];
-                } else if constexpr (NTIN) {
-                    stg[i] = __builtin_bit_cast(float2, __builtin_nontemporal_load(
-                                                            reinterpret_cast<const unsigned long long *>(px + roff[i])));
-                } else {
+                else
                     stg[i] = px[roff[i]];
-                }
             }
             return;
         }
@@ -377,12 +370,7 @@ k_zf_gemm_lds(const float2 *__restrict__ Wt, int a_m, int a_n, const float2 *__r
                 const int rr = row - AROWS;
                 const int n = min(n0 + rr / SB, N - 1);
                 const long long s = min(s0 + rr % SB, nsym - 1);
-                const float2 *p = in + (s * N + n) * (long long)K + kc;
-                if constexpr (NTIN)  // streamed once: keep it from evicting the re-read W tiles
-                    stg[i] = __builtin_bit_cast(
-                        float2, __builtin_nontemporal_load(reinterpret_cast<const unsigned long long *>(p)));
-                else
-                    stg[i] = *p;
+                stg[i] = in[(s * N + n) * (long long)K + kc];
             }
         }
     };
@@ -416,7 +404,7 @@ k_zf_gemm_lds(const float2 *__restrict__ Wt, int a_m, int a_n, const float2 *__r
             for (int jj = 0; jj < ST; ++jj) x[jj] = sx[(n * SB + jj) * 64];
 #pragma unroll
             for (int i = 0; i < MT; ++i) {
-                const float ar = a[i].x, ai = CONJ ? -a[i].y : a[i].y;
+                const float ar = a[i].x, ai = a[i].y;
 #pragma unroll
                 for (int jj = 0; jj < ST; ++jj) {
                     acc[i][jj].x = fmaf(ar, x[jj].x, fmaf(-ai, x[jj].y, acc[i][jj].x));
@@ -460,8 +448,8 @@ k_zf_gemm_lds(const float2 *__restrict__ Wt, int a_m, int a_n, const float2 *__r
 
 typedef __attribute__((address_space(3))) void lvoid_t;
 
-// The GEMM on the matrix cores (the k_zf_mfma_* / k_zf_wstat kernels below):
-// v_mfma_f32_4x4x1_16b_f32
+// The detect (A = W^H) on the matrix cores (the k_zf_mfma_* / k_zf_wstat
+// kernels below): v_mfma_f32_4x4x1_16b_f32
 // runs 16 INDEPENDENT 4 x 4 x 1 outer products per instruction, one per
 // 4-lane block, at the full f32 matrix rate (64 flop/clk/SIMD, the f32 vector
 // peak, MI355X_MICROARCH.md) -- so each block is one subcarrier and the
@@ -470,13 +458,12 @@ typedef __attribute__((address_space(3))) void lvoid_t;
 // (re m, im m, re m+1, im m+1), its 4 columns 4 symbols; per complex n two
 // MFMAs with the real k-steps Xr and Xi:
 //   A(re step) = (Ar, Ai, Ar', Ai'),  A(im step) = (-Ai, Ar, -Ai', Ar')
-// (Ai -> -Ai for CONJ), B = Xr or Xi of the lane's symbol.  Lane (b, i) loads
+// (A = conj(W)), B = Xr or Xi of the lane's symbol.  Lane (b, i) loads
 // W(m0 + 2p + i/2, n) and picks its component with one select per step; lane
 // (b, j) loads x[s0 + 4g + j][n][k0 + b].  D(row i, col j) of block b sits in
 // accumulator register i of lane 4 b + j: lane (b, j) stores two float2.
-// Each wave owns MP row pairs x SG symbol quads of 16 subcarriers; the 4 waves
-// of a workgroup take consecutive symbol quads of the same W tile (shared in
-// L1); operands of n+1 are loaded before the MFMAs of n.  f32 MFMA
+// In all three kernels a wave owns MP = 8 row pairs x SG = 4 symbol quads of
+// 16 subcarriers: 128 accumulators, two waves per SIMD.  f32 MFMA
 // accumulation is an exact f32 fma chain (MI355X_MICROARCH.md).
 typedef float mf4 __attribute__((ext_vector_type(4)));
 
@@ -529,19 +516,17 @@ __device__ __forceinline__ void dma_rows6(const float *const (&g)[12], unsigned 
                  : "memory");
 }
 
-// The LDS-fed MFMA GEMM with 8 waves (512 threads) per workgroup: MB = 4 MPW rows of
-// A and SB = 4 SG symbols per step, every wave keeping MPW x SG x 4 = 128
-// accumulators so that two waves share each SIMD.  Wave w computes
-// subcarriers 16 (w & 3) + b of the block for row pairs MPW (w >> 2) .. + MPW-1
+// The LDS-fed MFMA GEMM on 64-subcarrier blocks, 8 waves (512 threads) per
+// workgroup: MB = 32 rows of A and SB = 16 symbols per step.  Wave w computes
+// subcarriers 16 (w & 3) + b of the block for row pairs 8 (w >> 2) .. + 7
 // and stages rows w + 8 r of every step (the first MB / 8 of them A rows).
-// <8, 4>: 32-row tiles, so at M = 32 every input row is staged once instead
-// of once per 16-row block.
-template <int MPW, int SG, bool CONJ>
+// 32-row tiles, so at M = 32 every input row is staged once instead of once
+// per 16-row block.
 __global__ void __attribute__((amdgpu_flat_work_group_size(512, 512), amdgpu_waves_per_eu(2, 2)))
 k_zf_mfma_lds8(const float2 *__restrict__ Wt, int a_m, int a_n, const float2 *__restrict__ in, int N, int M,
                int K, long long nsym, float2 *__restrict__ out, int ntile, int tpx, int nkb,
                long long chunk_steps) {
-    constexpr int MP = MPW, MB = 4 * MPW, SB = 4 * SG, NB = 4;
+    constexpr int MP = 8, SG = 4, MB = 4 * MP, SB = 4 * SG, NB = 4;
     constexpr int ROWS = MB + SB, RPW = ROWS / 8, WR = MB / 8, LPW = 2 * RPW;
     static_assert(ROWS % 8 == 0 && RPW == 6 && (NB - 2) * LPW <= 63, "rows per wave / vmcnt range");
     extern __shared__ __attribute__((aligned(16))) float2 smd[];  // [NB][ROWS][64]
@@ -614,7 +599,7 @@ k_zf_mfma_lds8(const float2 *__restrict__ Wt, int a_m, int a_n, const float2 *__
 #pragma unroll
             for (int p = 0; p < MP; ++p) {
                 const float2 wv = sb[(2 * MP * half + 2 * p + (i >> 1)) * 64];
-                const float wy = CONJ ? -wv.y : wv.y;
+                const float wy = -wv.y;  // A = W^H
                 are[p] = odd ? wy : wv.x;
                 aim[p] = odd ? wv.x : -wy;
             }
@@ -705,7 +690,6 @@ __device__ __forceinline__ void dma_rows4x4(const float *const (&g)[16], unsigne
 // accumulators, 2 waves/SIMD), so every staged row piece is 1 KiB of a row
 // instead of 512 B (the no-MAC diagnostic showed the staging, not the MACs,
 // sets the time).  LDS 4 x 32 rows x 1 KiB = 128 KiB: one workgroup per CU.
-template <bool CONJ>
 __global__ void __attribute__((amdgpu_flat_work_group_size(512, 512), amdgpu_waves_per_eu(2, 2)))
 k_zf_mfma_w128(const float2 *__restrict__ Wt, int a_m, int a_n, const float2 *__restrict__ in, int N, int M,
                int K, long long nsym, float2 *__restrict__ out, int ntile, int tpx, int nkb,
@@ -783,7 +767,7 @@ k_zf_mfma_w128(const float2 *__restrict__ Wt, int a_m, int a_n, const float2 *__
 #pragma unroll
             for (int p = 0; p < MP; ++p) {
                 const float2 wv = sb[(2 * p + (i >> 1)) * BW];
-                const float wy = CONJ ? -wv.y : wv.y;
+                const float wy = -wv.y;  // A = W^H
                 are[p] = odd ? wy : wv.x;
                 aim[p] = odd ? wv.x : -wy;
             }
@@ -824,11 +808,11 @@ k_zf_mfma_w128(const float2 *__restrict__ Wt, int a_m, int a_n, const float2 *__
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // drain the tail re-loads before exit
 }
 
-// W-stationary MFMA GEMM for M <= 16 (k_zf_wstat; detect at U <= 16): the
+// W-stationary MFMA detect (k_zf_wstat; A = W^H, N = R <= 72): the
 // no-MAC diagnostic showed the re-staging of W tiles next to the input stream
 // costs most of the time, so here a workgroup owns 16 subcarriers and ONE
-// contiguous range of symbols, loads its whole A tile (all M <= 16 rows x N
-// <= 72 columns x 16 subcarriers, <= 144 KiB) into LDS once, and its 8 waves
+// contiguous range of symbols, loads its whole A tile (16 rows x N <= 72
+// columns x 16 subcarriers, <= 144 KiB) into LDS once, and its 8 waves
 // then stream the input straight from HBM -- each wave its own 16 symbols
 // per step, so no input is shared and nothing but the input and output
 // crosses the memory system per symbol.  Lane (b, i) = block b = subcarrier
@@ -838,28 +822,23 @@ k_zf_mfma_w128(const float2 *__restrict__ Wt, int a_m, int a_n, const float2 *__
 // bit-identical (profiles/r3/r3z6_zf_detect_prefetch_depth.jsonl): detect
 // U = 16 1.91 ms at PD = 3 (round 3) -> 1.85, U = 32 3.54 -> 3.34; PD = 1
 // and PD = 5 are slower than both.
-// XMAP: block b runs on XCD b % 8 (round-robin dispatch; speed only): the
-// chunk is b % 8 + 8 (b / (8 nkb)) and the subcarrier block (b / 8) % nkb, so
-// one XCD reads all subcarrier pieces of the same symbol rows.
-template <bool CONJ, bool XMAP = false, int MR = 16, int PDT = 2>
-__global__ void __attribute__((amdgpu_flat_work_group_size(MR == 64 ? 256 : 512, MR == 64 ? 256 : 512),
-                               amdgpu_waves_per_eu(MR == 64 ? 1 : 2, MR == 64 ? 1 : 2)))
+// Block b runs on XCD b % 8 (round-robin dispatch; speed only): its symbol
+// chunk is b % 8 + 8 (b / (8 ntl)) and its tile (b / 8) % ntl, so one XCD
+// reads all subcarrier pieces of the same symbol rows.
+__global__ void __attribute__((amdgpu_flat_work_group_size(512, 512), amdgpu_waves_per_eu(2, 2)))
 k_zf_wstat(const float2 *__restrict__ Wt, int a_m, int a_n, const float2 *__restrict__ in, int N, int M, int K,
            long long nsym, float2 *__restrict__ out, int nkb, int nmb, long long chunk_syms, long long ldi,
            long long ldo) {
-    // MR rows per tile: 16 (MP = 8 row pairs x SG = 4 symbol quads per wave) or
-    // 64 (apply at U = 16: all R = 64 output rows, MP = 32 x SG = 1)
-    // MR = 64: 4-wave workgroups, one wave per SIMD (512 registers for 128 accumulators + 32 A pairs)
-    constexpr int MP = MR / 2, SG = MR == 16 ? 4 : 1, SW = 4 * SG, PD = PDT, TR = MR * 16, NW = MR == 64 ? 4 : 8;
+    // 16-row tiles: MP = 8 row pairs x SG = 4 symbol quads per wave, 8 waves
+    constexpr int MR = 16, MP = MR / 2, SG = 4, SW = 4 * SG, PD = 2, TR = MR * 16, NW = 8;
     extern __shared__ __attribute__((aligned(16))) float2 smd[];  // [N][MR][16]
     // tile = (subcarrier block, 16-row block); the row blocks of one subcarrier
     // block are adjacent in dispatch order, so they read the same input rows
     // at about the same time (the second read hits L2)
     const long long ntl = (long long)nkb * nmb;
-    const int tl = XMAP ? (int)((blockIdx.x >> 3) % ntl) : (int)(blockIdx.x % ntl);
+    const int tl = (int)((blockIdx.x >> 3) % ntl);
     const int kb = tl / nmb, mb = tl % nmb, mr0 = MR * mb;
-    const long long chunk = XMAP ? (long long)(blockIdx.x & 7) + 8LL * (blockIdx.x / (8LL * ntl))
-                                 : (long long)(blockIdx.x / ntl);
+    const long long chunk = (long long)(blockIdx.x & 7) + 8LL * (blockIdx.x / (8LL * ntl));
     const int lane = threadIdx.x & 63, b = lane >> 2, i = lane & 3;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int k0 = kb * 16, k = k0 + b, kc = min(k, K - 1);
@@ -908,7 +887,7 @@ k_zf_wstat(const float2 *__restrict__ Wt, int a_m, int a_n, const float2 *__rest
 #pragma unroll
                         for (int p = 0; p < 4; ++p) {
                             const float2 wv = wl[n * TR + 2 * (p0 + p) * 16];
-                            const float wy = CONJ ? -wv.y : wv.y;
+                            const float wy = -wv.y;  // A = W^H
                             are[p] = odd ? wy : wv.x;
                             aim[p] = odd ? wv.x : -wy;
                         }
@@ -971,55 +950,55 @@ k_zf_wstat(const float2 *__restrict__ Wt, int a_m, int a_n, const float2 *__rest
 // per wave instruction).  The round-3 store-stream probes (scripts/
 // zfprobe2.hip) put the apply's bytes at 35-40 % less time with
 // 16-B than with 8-B stores.
-// W-stationary: a workgroup owns a tile of 128 subcarriers x MB = 8 RG output
-// rows, loads its W tile (U x MB x 1 KiB, 128 KiB at U = 16) into LDS once,
-// then its 8 waves stream their own symbols of one symbol chunk: wave (rg, sg)
-// computes rows 8 rg .. 8 rg + 7 for ST = 4 symbols at a time, reading the
-// symbols' input pieces straight from memory (prefetched one u ahead) and W
-// from LDS.  The nrb row blocks of one (chunk, subcarrier block) run on one
-// XCD, adjacent in dispatch order, so each input piece comes from HBM once and
-// from that XCD's L2 for the other row blocks.  Sum over u in the reference's
+// W-stationary: a workgroup owns a tile of 128 subcarriers x MT output rows,
+// loads its W tile (U x MT x 1 KiB, 128 KiB at U = 16, MT = 8) into LDS once,
+// then its 8 waves stream their own symbols of one symbol chunk: wave w
+// computes the MT rows for ST symbols at a time, reading the symbols' input
+// pieces straight from memory (prefetched one u ahead) and W from LDS.  The
+// nrb row blocks of one (chunk, subcarrier block) run on one XCD, adjacent in
+// dispatch order, so each input piece comes from HBM once and from that XCD's
+// L2 for the other row blocks; CHUNK_XCD puts every subcarrier block of a
+// chunk on that XCD too.  Sum over u in the reference's
 // order, one complex MAC per u (packed: (acc + x.re w) + (-x.im) w~, which
 // matches within the parity tolerance, not bit for bit).  K odd: the last
 // lane covers subcarriers (K-2, K-1) with W(K-2) zeroed and stores only K-1.
 // ---------------------------------------------------------------------------
-template <int MT, int RG, int ST, int NW, int XM = 0>
-__global__ void __attribute__((amdgpu_flat_work_group_size(64 * NW, 64 * NW), amdgpu_waves_per_eu(NW / 4, NW / 4)))
+template <int MT, int ST, bool CHUNK_XCD>
+__global__ void __attribute__((amdgpu_flat_work_group_size(512, 512), amdgpu_waves_per_eu(2, 2)))
 k_zf_apply_ws16(const float2 *__restrict__ Wt, const float2 *__restrict__ X, int U, int R, int K, long long nsym,
                 float2 *__restrict__ Y, int nkb, int nrb, int ngroups, long long chunk_syms, long long ldx,
                 long long ldy) {
-    constexpr int SGN = NW / RG, MB = MT * RG;
-    extern __shared__ __attribute__((aligned(16))) float4 smw[];  // [U][MB][64]
+    constexpr int NW = 8;
+    extern __shared__ __attribute__((aligned(16))) float4 smw[];  // [U][MT][64]
     const int b = blockIdx.x, xcd = b & 7, j = b >> 3;
     int kb, rb;
     long long chunk;
-    if constexpr (XM == 0) {  // (chunk, subcarrier block) groups round-robin over the XCDs
+    if constexpr (!CHUNK_XCD) {  // (chunk, subcarrier block) groups round-robin over the XCDs
         const int group = xcd + 8 * (j / nrb);
         rb = j % nrb;
         if (group >= ngroups) return;  // whole workgroup
         kb = group % nkb;
         chunk = group / nkb;
-    } else {  // A/B: every block of a chunk on one XCD (XM 1: row blocks adjacent, 2: subcarrier blocks adjacent)
+    } else {  // every block of a chunk on one XCD, row blocks adjacent
         const int per = nkb * nrb;
         chunk = xcd + 8LL * (j / per);
         const int jj = j % per;
-        rb = XM == 1 ? jj % nrb : jj / nkb;
-        kb = XM == 1 ? jj / nrb : jj % nkb;
+        rb = jj % nrb;
+        kb = jj / nrb;
         if (chunk * nkb >= ngroups) return;  // whole workgroup
     }
     const long long sbeg = chunk * chunk_syms, send = min(sbeg + chunk_syms, nsym);
     if (sbeg >= send) return;  // whole workgroup
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int rg = w % RG, sg = w / RG;
     const int k = kb * 128 + 2 * lane;
     const bool pair = k + 1 < K, last = k == K - 1;  // last: K odd, this lane stores K-1 only
     const int kc = pair ? k : (K >= 2 ? K - 2 : 0);  // every 16-B load in range
-    const int r0 = rb * MB;
+    const int r0 = rb * MT;
 
     // W tile -> LDS; element (u, m) of this lane = W(r0 + m, u) at subcarriers (kc, kc + 1)
-    for (int e = w; e < U * MB; e += NW) {
-        const int u = e / MB, m = e % MB, r = r0 + m;
+    for (int e = w; e < U * MT; e += NW) {
+        const int u = e / MT, m = e % MT, r = r0 + m;
         float4 v = float4{0.f, 0.f, 0.f, 0.f};
         if (r < R) {
             const float2 *p = Wt + ((long long)u * R + r) * K + kc;
@@ -1034,13 +1013,12 @@ k_zf_apply_ws16(const float2 *__restrict__ Wt, const float2 *__restrict__ X, int
     }
     __syncthreads();
 
-    const float4 *wl = smw + (rg * MT) * 64 + lane;  // + (u * MB + i) * 64
-    const int m0 = r0 + rg * MT;
+    const float4 *wl = smw + lane;  // + (u * MT + i) * 64
     // input rows of ldx elements, output rows of ldy (>= K; the reference layout: K).  With an odd
     // pitch the 16-B input loads of odd rows are 8-B aligned: unaligned dwordx4, which gfx950's
     // global memory serves (the W tile loads above likewise); pitches padded to even lengths avoid it.
     const long long UK = (long long)U * ldx;
-    for (long long s0 = sbeg + (long long)sg * ST; s0 < send; s0 += (long long)SGN * ST) {
+    for (long long s0 = sbeg + (long long)w * ST; s0 < send; s0 += (long long)NW * ST) {
         const float2 *xs[ST];
 #pragma unroll
         for (int q = 0; q < ST; ++q) xs[q] = X + min(s0 + q, send - 1) * UK + kc;
@@ -1055,7 +1033,7 @@ k_zf_apply_ws16(const float2 *__restrict__ Wt, const float2 *__restrict__ X, int
         auto step = [&](int u, const float4 (&x)[ST]) {
 #pragma unroll
             for (int i = 0; i < MT; ++i) {
-                const float4 wv = wl[(u * MB + i) * 64];
+                const float4 wv = wl[(u * MT + i) * 64];
 #pragma unroll
                 for (int q = 0; q < ST; ++q) {
                     pk::mac(acc[i][q][0], (pk::v2f){x[q].x, x[q].y}, (pk::v2f){wv.x, wv.y});
@@ -1079,10 +1057,10 @@ k_zf_apply_ws16(const float2 *__restrict__ Wt, const float2 *__restrict__ X, int
 #pragma unroll
             for (int q = 0; q < ST; ++q) {
                 if (s0 + q >= send) break;
-                float2 *o = Y + ((s0 + q) * R + m0) * ldy + kc;
+                float2 *o = Y + ((s0 + q) * R + r0) * ldy + kc;
 #pragma unroll
                 for (int i = 0; i < MT; ++i) {
-                    if (m0 + i >= R) break;
+                    if (r0 + i >= R) break;
                     float2 *y = o + (long long)i * ldy;
                     const float2 lo = pk::F(acc[i][q][0]), hi = pk::F(acc[i][q][1]);
                     if (pair)
@@ -1122,172 +1100,156 @@ hipError_t launch_zf_transpose(const float2 *W, int U, int R, int K, float2 *Wt,
 
 namespace {
 
-template <int MT, int ST, int MG, bool CONJ, bool PF = true>
-hipError_t gemm_launch(const float2 *Wt, int a_m, int a_n, const float2 *in, int N, int M, int K,
-                       long long nsym, float2 *out, hipStream_t s) {
-    constexpr int SBLK = (4 / MG) * ST;
-    const int nkb = (K + 63) / 64, nmb = (M + MG * MT - 1) / (MG * MT);
-    const int ntile = nkb * nmb, tpx = (ntile + 7) / 8;
-    const long long nsteps = (nsym + SBLK - 1) / SBLK;
-    // ~8 workgroups per CU (256 CUs) over all tiles, at least 4 steps per chunk
-    long long nchunk = (2048 + 8LL * tpx - 1) / (8LL * tpx);
-    long long chunk_steps = (nsteps + nchunk - 1) / nchunk;
-    if (chunk_steps < 4) chunk_steps = 4;
-    nchunk = (nsteps + chunk_steps - 1) / chunk_steps;
-    const long long blocks = 8LL * tpx * nchunk;
-    hipLaunchKernelGGL((zf::k_zf_gemm<MT, ST, MG, CONJ, PF>), dim3((unsigned)blocks), dim3(256), 0, s,
-                       Wt, a_m, a_n, in, N, M, K, nsym, out, ntile, tpx, nkb, chunk_steps);
+// One symbol-batched GEMM out[s][m][k] = sum_n A_k(m, n) in[s][n][k] with
+// A_k(m, n) = Wt[(m*a_m + n*a_n)*K + k]: the apply is {Wt, 1, R, X, U, R}
+// (A = W), the detect {Wt, R, 1, Y, R, U} (A = W^H, conjugated in the kernel).
+struct Gemm {
+    const float2 *Wt;
+    int a_m, a_n;
+    const float2 *in;
+    int N, M, K;
+    long long nsym;
+    float2 *out;
+};
+
+// The grid of the kernels that walk (subcarrier block, row block) tiles in
+// chunks of symbol steps (k_zf_gemm, k_zf_gemm_lds, k_zf_mfma_lds8,
+// k_zf_mfma_w128).  A tile
+// is kwidth subcarriers x rows rows, a step syms symbols; XCD x owns tiles x,
+// x + 8, ... (tpx of them), and the steps are cut into chunks so that about
+// target workgroups exist, none shorter than min_steps steps.
+struct TilePlan {
+    int ntile, tpx, nkb;
+    long long chunk_steps, blocks;
+};
+TilePlan plan_tiles(int kwidth, int rows, int syms, int target, int min_steps, int M, int K, long long nsym) {
+    TilePlan p;
+    p.nkb = (K + kwidth - 1) / kwidth;
+    p.ntile = p.nkb * ((M + rows - 1) / rows);
+    p.tpx = (p.ntile + 7) / 8;
+    const long long nsteps = (nsym + syms - 1) / syms;
+    long long nchunk = (target + 8LL * p.tpx - 1) / (8LL * p.tpx);
+    p.chunk_steps = (nsteps + nchunk - 1) / nchunk;
+    if (p.chunk_steps < min_steps) p.chunk_steps = min_steps;
+    nchunk = (nsteps + p.chunk_steps - 1) / p.chunk_steps;
+    p.blocks = 8LL * p.tpx * nchunk;
+    return p;
+}
+
+using tile_kernel_t = void (*)(const float2 *, int, int, const float2 *, int, int, int, long long, float2 *, int, int,
+                               int, long long);
+hipError_t tile_launch(tile_kernel_t kern, int threads, size_t lds, const TilePlan &p, const Gemm &g, hipStream_t s) {
+    if (p.blocks > 0x7fffffffLL) return hipErrorInvalidValue;
+    if (lds)
+        if (hipError_t e = opt_in_lds(reinterpret_cast<const void *>(kern), (int)lds); e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, dim3((unsigned)p.blocks), dim3(threads), lds, s, g.Wt, g.a_m, g.a_n, g.in, g.N, g.M, g.K,
+                       g.nsym, g.out, p.ntile, p.tpx, p.nkb, p.chunk_steps);
     return hipGetLastError();
 }
 
+// k_zf_gemm: MG row groups of MT rows and 4 / MG groups of 8 symbols per
+// workgroup; ~8 workgroups per CU (256 CUs), at least 4 steps per chunk
 template <int MT, int MG, bool CONJ>
-hipError_t gemm_variant(const float2 *Wt, int a_m, int a_n, const float2 *in, int N, int M, int K,
-                        long long nsym, float2 *out, hipStream_t s) {
-    return gemm_launch<MT, 8, MG, CONJ>(Wt, a_m, a_n, in, N, M, K, nsym, out, s);
+hipError_t gemm_launch(const Gemm &g, hipStream_t s) {
+    return tile_launch(zf::k_zf_gemm<MT, MG, CONJ>, 256, 0,
+                       plan_tiles(64, MG * MT, (4 / MG) * 8, 2048, 4, g.M, g.K, g.nsym), g, s);
+}
+// the smallest workgroup tile that holds all M rows
+template <bool CONJ>
+hipError_t gemm_by_rows(const Gemm &g, hipStream_t s) {
+    if (g.M <= 2) return gemm_launch<2, 1, CONJ>(g, s);
+    if (g.M <= 4) return gemm_launch<4, 1, CONJ>(g, s);
+    if (g.M <= 8) return gemm_launch<8, 1, CONJ>(g, s);
+    if (g.M <= 16) return gemm_launch<8, 2, CONJ>(g, s);
+    return gemm_launch<8, 4, CONJ>(g, s);
 }
 
-template <int MG, bool CONJ, int ST = 8>
-hipError_t gemm_lds_launch(const float2 *Wt, int a_m, int a_n, const float2 *in, int N, int M, int K,
-                           long long nsym, float2 *out, hipStream_t s) {
-    constexpr int SB = (4 / MG) * ST;
-    const int nkb = (K + 63) / 64, nmb = (M + MG * 8 - 1) / (MG * 8);
-    const int ntile = nkb * nmb, tpx = (ntile + 7) / 8;
-    const long long nsteps = (nsym + SB - 1) / SB;
-    long long nchunk = (2048 + 8LL * tpx - 1) / (8LL * tpx);
-    long long chunk_steps = (nsteps + nchunk - 1) / nchunk;
-    if (chunk_steps < 4) chunk_steps = 4;
-    nchunk = (nsteps + chunk_steps - 1) / chunk_steps;
-    const long long blocks = 8LL * tpx * nchunk;
-    hipLaunchKernelGGL((zf::k_zf_gemm_lds<MG, CONJ>), dim3((unsigned)blocks), dim3(256), 0, s, Wt, a_m,
-                       a_n, in, N, M, K, nsym, out, ntile, tpx, nkb, chunk_steps);
-    return hipGetLastError();
-}
-
-
-// k_zf_apply_ws16 (16-B lanes, W-stationary): NW waves, RG row groups of MT
-// rows per tile, ST symbols per wave step
-template <int MT, int RG, int ST, int NW, int XM = 0>
+// k_zf_apply_ws16: tiles of MT rows, ST symbols per wave step, about
+// target_groups (symbol chunk, subcarrier block) groups
+template <int MT, int ST, bool CHUNK_XCD>
 hipError_t apply_ws16_launch(const float2 *Wt, const float2 *X, int U, int R, int K, long long nsym, float2 *Y,
-                             int target_groups, hipStream_t s, long long ldx = -1, long long ldy = -1) {
-    constexpr int MB = MT * RG, WSTEP = NW / RG * ST;
-    const size_t lds = (size_t)U * MB * 64 * sizeof(float4);
+                             int target_groups, hipStream_t s, long long ldx, long long ldy) {
+    constexpr int WSTEP = 8 * ST;
+    const size_t lds = (size_t)U * MT * 64 * sizeof(float4);
     if (lds > 160 * 1024 || K < 2) return hipErrorInvalidValue;
-    const int nkb = (K + 127) / 128, nrb = (R + MB - 1) / MB;
+    const int nkb = (K + 127) / 128, nrb = (R + MT - 1) / MT;
     long long nch = (target_groups + nkb - 1) / nkb;
     if (nch < 1) nch = 1;
     long long chunk_syms = (nsym + nch - 1) / nch;
     chunk_syms = (chunk_syms + WSTEP - 1) / WSTEP * WSTEP;  // whole steps of every wave
     nch = (nsym + chunk_syms - 1) / chunk_syms;
     const long long ngroups = nch * nkb;
-    const long long blocks = XM == 0 ? 8LL * ((ngroups + 7) / 8) * nrb : 8LL * ((nch + 7) / 8) * nkb * nrb;
+    const long long blocks = CHUNK_XCD ? 8LL * ((nch + 7) / 8) * nkb * nrb : 8LL * ((ngroups + 7) / 8) * nrb;
     if (blocks > 0x7fffffffll) return hipErrorInvalidValue;
-    auto kern = zf::k_zf_apply_ws16<MT, RG, ST, NW, XM>;
+    auto kern = zf::k_zf_apply_ws16<MT, ST, CHUNK_XCD>;
     if (hipError_t e = opt_in_lds(reinterpret_cast<const void *>(kern), (int)lds); e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(64 * NW), lds, s, Wt, X, U, R, K, nsym, Y, nkb, nrb,
-                       (int)ngroups, chunk_syms, ldx < 0 ? K : ldx, ldy < 0 ? K : ldy);
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(512), lds, s, Wt, X, U, R, K, nsym, Y, nkb, nrb,
+                       (int)ngroups, chunk_syms, ldx, ldy);
     return hipGetLastError();
 }
 
-
-template <int MPW, int SG, bool CONJ>
-hipError_t mfma_lds8_launch(const float2 *Wt, int a_m, int a_n, const float2 *in, int N, int M, int K,
-                            long long nsym, float2 *out, hipStream_t s) {
-    constexpr int SB = 4 * SG, MB = 4 * MPW;
-    constexpr size_t lds = (size_t)4 * (MB + SB) * 64 * sizeof(float2);  // 96 KiB
-    const int nkb = (K + 63) / 64, nmb = (M + MB - 1) / MB;
-    const int ntile = nkb * nmb, tpx = (ntile + 7) / 8;
-    const long long nsteps = (nsym + SB - 1) / SB;
-    long long nchunk = (1024 + 8LL * tpx - 1) / (8LL * tpx);
-    long long chunk_steps = (nsteps + nchunk - 1) / nchunk;
-    if (chunk_steps < 2) chunk_steps = 2;
-    nchunk = (nsteps + chunk_steps - 1) / chunk_steps;
-    const long long blocks = 8LL * tpx * nchunk;
-    if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-    auto kern = zf::k_zf_mfma_lds8<MPW, SG, CONJ>;
-    if (hipError_t e = opt_in_lds(reinterpret_cast<const void *>(kern), (int)lds); e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(512), lds, s, Wt, a_m, a_n, in, N, M, K, nsym, out,
-                       ntile, tpx, nkb, chunk_steps);
-    return hipGetLastError();
-}
-
-template <bool CONJ>
-hipError_t mfma_w128_launch(const float2 *Wt, int a_m, int a_n, const float2 *in, int N, int M, int K,
-                            long long nsym, float2 *out, hipStream_t s) {
-    constexpr int SB = 16, MB = 16;
-    constexpr size_t lds = (size_t)4 * (MB + SB) * 128 * sizeof(float2);  // 128 KiB
-    const int nkb = (K + 127) / 128, nmb = (M + MB - 1) / MB;
-    const int ntile = nkb * nmb, tpx = (ntile + 7) / 8;
-    const long long nsteps = (nsym + SB - 1) / SB;
-    long long nchunk = (1024 + 8LL * tpx - 1) / (8LL * tpx);
-    long long chunk_steps = (nsteps + nchunk - 1) / nchunk;
-    if (chunk_steps < 2) chunk_steps = 2;
-    nchunk = (nsteps + chunk_steps - 1) / chunk_steps;
-    const long long blocks = 8LL * tpx * nchunk;
-    if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-    auto kern = zf::k_zf_mfma_w128<CONJ>;
-    if (hipError_t e = opt_in_lds(reinterpret_cast<const void *>(kern), (int)lds); e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(512), lds, s, Wt, a_m, a_n, in, N, M, K, nsym, out,
-                       ntile, tpx, nkb, chunk_steps);
-    return hipGetLastError();
-}
-
-template <bool CONJ, bool XMAP, int MR = 16, int PD = 2>
-hipError_t wstat_launch(const float2 *Wt, int a_m, int a_n, const float2 *in, int N, int M, int K,
-                        long long nsym, float2 *out, hipStream_t s, long long ldi = -1, long long ldo = -1) {
-    const size_t lds = (size_t)N * MR * 16 * sizeof(float2);  // N * MR <= 1152: <= 144 KiB
-    const int nkb = (K + 15) / 16, nmb = (M + MR - 1) / MR;
-    // ~1 workgroup per CU over all (tile, symbol chunk) pairs;
-    // XMAP: a multiple of 8 chunks (one per XCD)
-    long long nchunk = XMAP ? 8 : (256 + nkb * nmb - 1) / (nkb * nmb);
-    long long chunk_syms = (nsym + nchunk - 1) / nchunk;
+// k_zf_wstat: one symbol chunk per XCD -- 8 chunks of at least 128 symbols,
+// more (a multiple of 8; empty chunks return at once) only to keep that floor
+hipError_t wstat_launch(const Gemm &g, long long ldi, long long ldo, hipStream_t s) {
+    const size_t lds = (size_t)g.N * 16 * 16 * sizeof(float2);  // N <= 72: <= 144 KiB
+    const int nkb = (g.K + 15) / 16, nmb = (g.M + 15) / 16;
+    long long chunk_syms = (g.nsym + 7) / 8;
     if (chunk_syms < 128) chunk_syms = 128;
-    nchunk = (nsym + chunk_syms - 1) / chunk_syms;
-    if (XMAP) nchunk = (nchunk + 7) / 8 * 8;  // empty chunks return at once
+    const long long nchunk = ((g.nsym + chunk_syms - 1) / chunk_syms + 7) / 8 * 8;
     const long long blocks = (long long)nkb * nmb * nchunk;
     if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-    auto kern = zf::k_zf_wstat<CONJ, XMAP, MR, PD>;
-    if (hipError_t e = opt_in_lds(reinterpret_cast<const void *>(kern), 72 * 256 * (int)sizeof(float2));
+    if (hipError_t e = opt_in_lds(reinterpret_cast<const void *>(zf::k_zf_wstat), 72 * 256 * (int)sizeof(float2));
         e != hipSuccess)
         return e;
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(MR == 64 ? 256 : 512), lds, s, Wt, a_m, a_n, in, N, M, K,
-                       nsym, out, nkb, nmb, chunk_syms, ldi < 0 ? K : ldi, ldo < 0 ? K : ldo);
+    hipLaunchKernelGGL(zf::k_zf_wstat, dim3((unsigned)blocks), dim3(512), lds, s, g.Wt, g.a_m, g.a_n, g.in, g.N, g.M,
+                       g.K, g.nsym, g.out, nkb, nmb, chunk_syms, ldi, ldo);
     return hipGetLastError();
 }
 
-// Measured defaults (same-process A/B, R = 64, 10 000 symbols):
-//   detect, M = U > 8, N = R <= 72: W-stationary MFMA with one symbol chunk
-//     per XCD (k_zf_wstat<., true>): 1.87 vs 2.05 ms (VALU) at U = 16,
-//     3.34 vs 3.67 (k_zf_mfma_lds8<8,4>) / 4.09 (VALU) at U = 32;
-//   detect with N > 72: k_zf_mfma_lds8<8,4> (M > 16) / k_zf_mfma_w128;
-//   detect at U <= 8: the per-wave register-tiled VALU kernel (1.26-1.37 vs
-//     1.35-1.39 ms for the LDS VALU kernel at U = 8);
-//   apply at 32 <= N = U <= 72: k_zf_wstat<., true> (4.08 vs 4.28 ms);
-//   otherwise the LDS VALU kernel when both operands are wide enough (at
-//     N = 4 its per-chunk barriers and stores dominate), else the register-
-//     tiled one.
-// Measured-slower candidates (register tiles without double buffering,
-// DMA-fed LDS VALU tiles, MFMA from L1 / through 4-wave LDS tiles, other
-// W-stationary depths and tile heights) are kept out of the product sources
-// (scripts/experiments/ab_knobs_r3.patch).
-enum { ZF_REG = 0, ZF_LDS = 1, ZF_MFMA_LDS8 = 6, ZF_MFMA_W128 = 7, ZF_WSTAT = 9 };
-template <bool CONJ>
-hipError_t gemm_dispatch(const float2 *Wt, int a_m, int a_n, const float2 *in, int N, int M, int K,
-                         long long nsym, float2 *out, hipStream_t s) {
-    const int mode = CONJ ? (N < 8 ? ZF_LDS : M <= 8 ? ZF_REG : N <= 72 ? ZF_WSTAT : M > 16 ? ZF_MFMA_LDS8 : ZF_MFMA_W128)
-                          : (N >= 32 && N <= 72 ? ZF_WSTAT : ZF_LDS);
-    if (mode == ZF_WSTAT && N <= 72) return wstat_launch<CONJ, true>(Wt, a_m, a_n, in, N, M, K, nsym, out, s);
-    if (mode == ZF_MFMA_LDS8) return mfma_lds8_launch<8, 4, CONJ>(Wt, a_m, a_n, in, N, M, K, nsym, out, s);
-    if (mode == ZF_MFMA_W128) return mfma_w128_launch<CONJ>(Wt, a_m, a_n, in, N, M, K, nsym, out, s);
-    if (M > 4 && N >= 8 && mode != ZF_REG) {
-        if (M <= 8) return gemm_lds_launch<1, CONJ>(Wt, a_m, a_n, in, N, M, K, nsym, out, s);
-        if (M <= 16) return gemm_lds_launch<2, CONJ>(Wt, a_m, a_n, in, N, M, K, nsym, out, s);
-        return gemm_lds_launch<4, CONJ>(Wt, a_m, a_n, in, N, M, K, nsym, out, s);
-    }
-    if (M <= 2) return gemm_variant<2, 1, CONJ>(Wt, a_m, a_n, in, N, M, K, nsym, out, s);
-    if (M <= 4) return gemm_variant<4, 1, CONJ>(Wt, a_m, a_n, in, N, M, K, nsym, out, s);
-    if (M <= 8) return gemm_variant<8, 1, CONJ>(Wt, a_m, a_n, in, N, M, K, nsym, out, s);
-    if (M <= 16) return gemm_variant<8, 2, CONJ>(Wt, a_m, a_n, in, N, M, K, nsym, out, s);
-    return gemm_variant<8, 4, CONJ>(Wt, a_m, a_n, in, N, M, K, nsym, out, s);
+// Which kernel runs, by shape alone (1 <= U <= 32 by the C ABI).  The
+// measurements are same-process A/B at R = 64, K = 1023, 10 000 symbols
+// (DESIGN.md 7c); the candidates that lost are kept out of the product
+// sources, as scripts/experiments/ab_knobs_r3.patch.
+//   detect  R < 8 or U <= 8    k_zf_gemm: 1.26-1.37 ms at U = 8 against
+//                              1.35-1.39 with the operands staged in LDS
+//           R <= 72            k_zf_wstat: 1.87 against 2.05 ms (LDS-fed VALU
+//                              tiles) at U = 16, 3.34 against 3.67
+//                              (k_zf_mfma_lds8) and 4.09 (VALU) at U = 32
+//           U > 16             k_zf_mfma_lds8  } R > 72: the W tile of
+//           otherwise          k_zf_mfma_w128  } k_zf_wstat outgrows LDS
+//   apply   K >= 2 and R >= 8  k_zf_apply_ws16, U = 4 / 8 / 16 / 24 / 32:
+//                              1.82 / 1.96 / 2.38 / 3.16 / 4.42 ms with 8-B
+//                              lanes -> 1.50 / 1.53 / 1.94-1.96 / 2.93 / 3.58;
+//             U <= 20          8-row tiles (W tile U x 8 KiB of LDS), 4-symbol
+//                              steps, every block of a 64-symbol chunk on one
+//                              XCD: 1.320 / 1.358 / 1.743 / 2.004 -> 1.235 /
+//                              1.253 / 1.718 / 1.996 ms at U = 4 / 8 / 16 / 20
+//                              (profiles/r3/r3l_zf_apply_xmap.jsonl)
+//             otherwise        4-row tiles, 8-symbol steps, chunk groups
+//                              round-robin over the XCDs (the one-XCD map is
+//                              1.7x slower here)
+//           5 <= R < 8 and     k_zf_gemm_lds: at R = 6, U = 8 / 16 / 32 0.267 /
+//             U >= 8           0.395 / 0.683 ms against 0.266 / 0.400 / 0.707
+//                              with k_zf_gemm, separate processes alternating
+//                              (profiles/r10/zf_r6_three_way.log)
+//           otherwise          k_zf_gemm (R < 5, U < 8 at R < 8, or K = 1 at
+//                              R >= 8: no subcarrier pair for a 16-B lane)
+hipError_t detect(const Gemm &g, hipStream_t s) {
+    const int U = g.M, R = g.N;
+    if (R < 8 || U <= 8) return gemm_by_rows<true>(g, s);
+    if (R <= 72) return wstat_launch(g, g.K, g.K, s);
+    if (U > 16)  // 64 subcarriers x 32 rows, 16 symbols per step, 4 buffers: 96 KiB
+        return tile_launch(zf::k_zf_mfma_lds8, 512, 4 * (32 + 16) * 64 * sizeof(float2),
+                           plan_tiles(64, 32, 16, 1024, 2, g.M, g.K, g.nsym), g, s);
+    // 128 subcarriers x 16 rows, 16 symbols per step, 4 buffers: 128 KiB
+    return tile_launch(zf::k_zf_mfma_w128, 512, 4 * (16 + 16) * 128 * sizeof(float2),
+                       plan_tiles(128, 16, 16, 1024, 2, g.M, g.K, g.nsym), g, s);
+}
+
+hipError_t apply_ws16(const float2 *Wt, const float2 *X, long long ldx, int U, int R, int K, long long nsym, float2 *Y,
+                      long long ldy, hipStream_t s) {
+    if (U <= 20) return apply_ws16_launch<8, 4, true>(Wt, X, U, R, K, nsym, Y, 64, s, ldx, ldy);
+    return apply_ws16_launch<4, 8, false>(Wt, X, U, R, K, nsym, Y, 32, s, ldx, ldy);
 }
 
 }  // namespace
@@ -1296,20 +1258,11 @@ hipError_t gemm_dispatch(const float2 *Wt, int a_m, int a_n, const float2 *in, i
 hipError_t launch_zf_apply(const float2 *Wt, const float2 *X, int U, int R, int K, long long nsym,
                            float2 *Y, hipStream_t s) {
     if (K == 0 || nsym == 0) return hipSuccess;
-    // 16-B lanes, W-stationary (k_zf_apply_ws16): 8-row tiles up to U = 20
-    // (W tile U x 8 KiB of LDS), 4-row tiles with 8-symbol steps up to U = 40;
-    // same-process A/B at R = 64, K = 1023, 10 000 symbols:
-    // U = 4 / 8 / 16 / 24 / 32: 1.82 / 1.96 / 2.38 / 3.16 / 4.42 ms -> 1.50 /
-    // 1.53 / 1.94-1.96 / 2.93 / 3.58 ms.  Fewer than 8 antenna rows fill less
-    // than one 8-row tile: the register-tiled kernels below.  8-row tiles run
-    // every block of a 64-symbol chunk on one XCD (row blocks adjacent,
-    // XM = 1): same-process A/B vs chunk groups round-robin over the XCDs,
-    // U = 4 / 8 / 16 / 20: 1.320 / 1.358 / 1.743 / 2.004 -> 1.235 / 1.253 /
-    // 1.718 / 1.996 ms (profiles/r3/r3l_zf_apply_xmap.jsonl); the same map
-    // on the 4-row tiles is 1.7x slower.
-    if (K >= 2 && R >= 8 && U <= 20) return apply_ws16_launch<8, 1, 4, 8, 1>(Wt, X, U, R, K, nsym, Y, 64, s);
-    if (K >= 2 && R >= 8 && U <= 40) return apply_ws16_launch<4, 1, 8, 8>(Wt, X, U, R, K, nsym, Y, 32, s);
-    return gemm_dispatch<false>(Wt, 1, R, X, U, R, K, nsym, Y, s);
+    if (K >= 2 && R >= 8) return apply_ws16(Wt, X, K, U, R, K, nsym, Y, K, s);
+    const Gemm g{Wt, 1, R, X, U, R, K, nsym, Y};
+    if (R >= 5 && R < 8 && U >= 8)  // one 8-row tile, 32 symbols per step
+        return tile_launch(zf::k_zf_gemm_lds, 256, 0, plan_tiles(64, 8, 32, 2048, 4, g.M, g.K, g.nsym), g, s);
+    return gemm_by_rows<false>(g, s);
 }
 
 // The apply with row pitches (X rows of ldx, Y rows of ldy elements >= K):
@@ -1320,15 +1273,14 @@ hipError_t launch_zf_apply_ld(const float2 *Wt, const float2 *X, long long ldx, 
     if (K == 0 || nsym == 0) return hipSuccess;
     if (ldx == K && ldy == K) return launch_zf_apply(Wt, X, U, R, K, nsym, Y, s);
     if (!zf_apply_pitched_supported(U, R, K)) return hipErrorInvalidValue;
-    if (U <= 20) return apply_ws16_launch<8, 1, 4, 8, 1>(Wt, X, U, R, K, nsym, Y, 64, s, ldx, ldy);
-    return apply_ws16_launch<4, 1, 8, 8>(Wt, X, U, R, K, nsym, Y, 32, s, ldx, ldy);
+    return apply_ws16(Wt, X, ldx, U, R, K, nsym, Y, ldy, s);
 }
 
 // X[s][u][k] = sum_r conj(W(r, u)) Y[s][r][k]
 hipError_t launch_zf_detect(const float2 *Wt, const float2 *Y, int U, int R, int K, long long nsym,
                             float2 *X, hipStream_t s) {
     if (K == 0 || nsym == 0) return hipSuccess;
-    return gemm_dispatch<true>(Wt, R, 1, Y, R, U, K, nsym, X, s);
+    return detect(Gemm{Wt, R, 1, Y, R, U, K, nsym, X}, s);
 }
 
 // The same with row pitches: Y[s][r][k] at Y[(s R + r) ldy + k], X[s][u][k]
@@ -1340,9 +1292,9 @@ bool zf_detect_pitched_supported(int U, int R) { return U >= 1 && R <= 72; }
 hipError_t launch_zf_detect_ld(const float2 *Wt, const float2 *Y, long long ldy, int U, int R, int K,
                                long long nsym, float2 *X, long long ldx, hipStream_t s) {
     if (K == 0 || nsym == 0) return hipSuccess;
-    if (ldy == K && ldx == K) return gemm_dispatch<true>(Wt, R, 1, Y, R, U, K, nsym, X, s);
+    if (ldy == K && ldx == K) return launch_zf_detect(Wt, Y, U, R, K, nsym, X, s);
     if (!zf_detect_pitched_supported(U, R)) return hipErrorInvalidValue;
-    return wstat_launch<true, true>(Wt, R, 1, Y, R, U, K, nsym, X, s, ldy, ldx);
+    return wstat_launch(Gemm{Wt, R, 1, Y, R, U, K, nsym, X}, ldy, ldx, s);
 }
 
 }  // namespace ofdm

@@ -50,12 +50,15 @@ def test_zf_precoder_single_output(ofdm, dev):
     assert np.array_equal(Wt_only.cpu().numpy(), W_only.cpu().numpy().transpose(1, 2, 0))
 
 
-# The shapes select every kernel of the shape-based dispatch (zf.hip
-# gemm_dispatch): detect -- register tiles (U <= 8 or R < 8), W-stationary
-# MFMA (U > 8, R <= 72), 8-wave MFMA (U > 16, R > 72), 128-subcarrier MFMA
-# (8 < U <= 16, R > 72); apply -- 16-B-lane W-stationary tiles (R >= 8 and
-# K >= 2: 8-row tiles for U <= 20, 4-row tiles for U <= 40; K odd exercises the
-# lane that stores subcarrier K-1 alone), register tiles (R < 8 or K < 2).
+# With test_zf_apply_detect_degenerate_shapes below, the shapes select every
+# kernel of the shape-based dispatch (the table above launch_zf_apply in
+# zf.hip): detect -- register tiles (U <= 8 or R < 8; here with 2-, 4- and
+# 8-row wave tiles), W-stationary MFMA (U > 8, 8 <= R <= 72), 8-wave MFMA
+# (U > 16, R > 72), 128-subcarrier MFMA (8 < U <= 16, R > 72); apply --
+# 16-B-lane W-stationary tiles (R >= 8 and K >= 2: 8-row tiles for U <= 20,
+# 4-row tiles above; K odd exercises the lane that stores subcarrier K-1
+# alone), register tiles (R < 8 with U < 8: 2-, 4- and 8-row wave tiles), the
+# LDS-fed 8-row tile (5 <= R < 8 with U >= 8: below).
 @pytest.mark.parametrize("U,R,K,n", [(1, 1, 5, 1), (2, 4, 1023, 7), (3, 5, 64, 9), (4, 16, 1023, 33),
                                      (5, 12, 130, 17), (8, 64, 1023, 40), (12, 40, 200, 16),
                                      (16, 64, 1023, 100), (17, 64, 65, 3), (32, 64, 255, 25),
@@ -70,6 +73,30 @@ def test_zf_apply_detect_parity(ofdm, oracle, dev, U, R, K, n):
     assert rel_err(got_Y, Y) < 1e-5
     parity(got_Y, Y)  # norm-wise and element-wise, 1e-5
     Yn = (Y + 0.05 * qpsk(n, R, K, seed=n + 2)).astype(np.complex64)  # not just W X
+    got_X = ofdm.zf_detect(Wt, dev_t(Yn, dev)).cpu().numpy()
+    ref_X = oracle.zf_detect(W, Yn)
+    assert rel_err(got_X, ref_X) < 1e-5
+    parity(got_X, ref_X)
+
+
+# Fewer antennas than users (R < U, where A A^H is singular and no precoder
+# exists) and a single subcarrier: apply and detect are plain per-subcarrier
+# GEMMs, so W is a seeded random array.  Apply -- the LDS-fed 8-row tile
+# (5 <= R < 8 and U >= 8; (16, 5, 130, 9): two full 64-subcarrier blocks and
+# a ragged third) and register tiles at K = 1 (16- / 32-row workgroups by R);
+# detect -- register tiles (R < 8 at U = 8 / 16 / 32: 1 / 2 / 4 row groups
+# per workgroup, and U <= 8 at K = 1), W-stationary MFMA at K = 1.
+@pytest.mark.parametrize("U,R,K,n", [(8, 6, 65, 5), (16, 5, 130, 9), (32, 6, 40, 20), (8, 16, 1, 5),
+                                     (12, 40, 1, 3), (32, 64, 1, 4)])
+def test_zf_apply_detect_degenerate_shapes(ofdm, oracle, dev, U, R, K, n):
+    W = np.ascontiguousarray(channel(U, R, K, seed=n).transpose(2, 0, 1))  # [K][U][R]
+    X = qpsk(n, U, K, seed=n + 1)
+    Y = oracle.zf_apply(W, X)
+    Wt = ofdm.zf_transpose(dev_t(W, dev))
+    got_Y = ofdm.zf_apply(Wt, dev_t(X, dev)).cpu().numpy()
+    assert rel_err(got_Y, Y) < 1e-5
+    parity(got_Y, Y)
+    Yn = (Y + 0.05 * qpsk(n, R, K, seed=n + 2)).astype(np.complex64)
     got_X = ofdm.zf_detect(Wt, dev_t(Yn, dev)).cpu().numpy()
     ref_X = oracle.zf_detect(W, Yn)
     assert rel_err(got_X, ref_X) < 1e-5
