@@ -27,6 +27,13 @@
  *   the default stream).  Calls are asynchronous on that stream.
  *   Return value: 0 (OFDM_OK) or a negative OFDM_E_* code; ofdm_last_error()
  *   describes the last failure on the calling thread.
+ *   Alignment of device pointers (OFDM_E_ARG otherwise, before any device
+ *   work): 16 bytes for the sample input of every frame, symbol and MRC entry
+ *   -- d_iq / d_Y / d_sym of ofdm_frame_*, ofdm_symbols_demod, ofdm_mrc_demod
+ *   and ofdm_mrc_numerator (rows inside the buffer need 8 bytes only, sc16 rows
+ *   4: any cp_len works) -- and for the pointers an entry's own comment names;
+ *   256 bytes for d_ws.  Every other pointer needs the natural alignment of its
+ *   element only: 8 bytes for ofdm_cf32 and the 64-bit words, 4 for float.
  */
 #ifndef OFDM_LSMRC_H_
 #define OFDM_LSMRC_H_

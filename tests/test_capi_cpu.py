@@ -77,6 +77,37 @@ def test_argument_validation_without_device(ofdm):
     assert L.ofdm_frame_demod(fake, 0, 11, 64, 1024, 0, fake, fake, need, fake, None) == 0
 
 
+def test_stated_alignments_are_refused_without_device(ofdm):
+    """The header's alignment paragraph: the sample input of the frame, symbol
+    and MRC entries 16 bytes, the workspace 256 -- refused with OFDM_E_ARG
+    before any device work when only the element's natural 8 bytes hold (the
+    containment tests run every pointer at exactly its stated alignment and
+    none below it)."""
+    L = ofdm.lib()
+    P = ctypes.c_void_p
+    ok, off8 = P(4096), P(4096 + 8)
+    need = L.ofdm_frame_workspace_bytes(2, 5, 8, 1024)
+    calls = [
+        lambda: L.ofdm_mrc_demod(off8, 3, ok, ok, 4, 1024, ok, None),
+        lambda: L.ofdm_mrc_numerator(off8, 3, ok, 4, 1024, ok, None),
+        lambda: L.ofdm_frame_estimate(off8, 2, 5, 8, 1024, 0, ok, ok, need, None),
+        lambda: L.ofdm_frame_combine(off8, 2, 5, 8, 1024, 0, ok, need, ok, None),
+        lambda: L.ofdm_frame_demod_freq(off8, 2, 5, 8, 1024, ok, ok, need, ok, None),
+        lambda: L.ofdm_frame_demod_freq_mfma(off8, 2, 5, 8, 1024, ok, ok, need, ok, None),
+        lambda: L.ofdm_frame_ls_partial(off8, 2, 5, 8, 1024, 0, ok, ok, need, ok, None),
+        lambda: L.ofdm_frame_cfo_estimate(off8, 2, 5, 8, 1024, 16, 0, None, ok, None),
+        lambda: L.ofdm_symbols_demod(off8, 3, 8, 1024, 0, ok, need, 0, ok, None),
+        lambda: L.ofdm_frame_demod(ok, 2, 5, 8, 1024, 0, ok, P(4096 + 128), need, ok, None),  # the workspace
+    ]
+    for i, call in enumerate(calls):
+        assert call() == -1, i
+        assert b"aligned" in L.ofdm_last_error(), (i, L.ofdm_last_error())
+    # the natural alignment is enough for every other pointer: these get past the alignment checks
+    assert L.ofdm_mrc_demod(ok, 3, off8, P(4096 + 4), 4, 8193, off8, None) == -3  # (refused for C alone)
+    assert L.ofdm_frame_combine(ok, 2, 5, 8, 1024, 0, ok, need, off8, None) == -1
+    assert b"holds no estimate" in L.ofdm_last_error()
+
+
 def test_zf_argument_validation_without_device(ofdm):
     """ofdm_zf_* reject unsupported geometry and null pointers before any launch."""
     L = ofdm.lib()
