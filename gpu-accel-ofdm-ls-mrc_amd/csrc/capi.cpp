@@ -12,6 +12,7 @@
 #include <string>
 
 #include "../../include/ofdm_lsmrc.h"
+#include "../../include/ofdm_lsmrc_acquire.h"
 #include "launch.hpp"
 
 namespace {
@@ -724,6 +725,41 @@ int ofdm_frame_demod_cfo(const ofdm_cf32 *d_iq, long long nframes, int S, int R,
     if (!d_X) return fail(OFDM_E_ARG, "%s: null pilots", fn);
     if (nframes == 0) return OFDM_OK;
     return demod_1024(ofdm::iq_f32(F2(d_iq), d_eps), nframes, S, R, prefix, d_X, d_ws, ws_bytes_, d_out, stream);
+}
+
+// Integer carrier offset (include/ofdm_lsmrc_acquire.h): the refusals in the
+// order the header lists them, before any HIP call.
+int ofdm_frame_cfo_acquire(const ofdm_cf32 *d_iq, long long nframes, int S, int R, int C, int cp_len,
+                           const ofdm_cf32 *d_X, int max_shift, float min_ratio, const float *d_eps_in,
+                           float *d_eps_out, int *d_shift, float *d_metric, ofdm_stream_t stream) {
+    static const char *fn = "ofdm_frame_cfo_acquire";
+    if (nframes < 0) return fail(OFDM_E_ARG, "%s: nframes < 0", fn);
+    if (S < 2) return fail(OFDM_E_ARG, "%s: S=%d, a frame needs a pilot and >= 1 data symbol", fn, S);
+    if (R < 1) return fail(OFDM_E_ARG, "%s: R=%d < 1", fn, R);
+    if (cp_len < 0 || cp_len > C) return fail(OFDM_E_ARG, "%s: cp_len=%d out of [0, C]", fn, cp_len);
+    if (nframes > 0 && !d_iq) return fail(OFDM_E_ARG, "%s: null d_iq", fn);
+    if (nframes > 0 && !d_X) return fail(OFDM_E_ARG, "%s: null d_X", fn);
+    if (nframes > 0 && !d_eps_out) return fail(OFDM_E_ARG, "%s: null d_eps_out", fn);
+    if (!aligned(d_iq, 16)) return fail(OFDM_E_ARG, "%s: d_iq must be 16-byte aligned", fn);
+    if (max_shift < 1 || max_shift > OFDM_ACQ_MAX_SHIFT)
+        return fail(OFDM_E_ARG, "%s: max_shift=%d out of [1, %d]", fn, max_shift, OFDM_ACQ_MAX_SHIFT);
+    if (!(min_ratio >= 1.f && min_ratio <= 3.402823466e38f))
+        return fail(OFDM_E_ARG, "%s: min_ratio=%g, the gate needs a finite ratio >= 1", fn, (double)min_ratio);
+    if (nframes > 0) {
+        const uintptr_t e0 = reinterpret_cast<uintptr_t>(d_eps_out), e1 = e0 + (uintptr_t)nframes * sizeof(float);
+        const uintptr_t m0 = reinterpret_cast<uintptr_t>(d_metric),
+                        m1 = m0 + (uintptr_t)nframes * (2 * max_shift + 1) * sizeof(float);
+        const uintptr_t s0 = reinterpret_cast<uintptr_t>(d_shift), s1 = s0 + (uintptr_t)nframes * sizeof(int);
+        if (d_metric && e0 < m1 && m0 < e1) return fail(OFDM_E_ARG, "%s: d_eps_out overlaps d_metric", fn);
+        if (d_shift && e0 < s1 && s0 < e1) return fail(OFDM_E_ARG, "%s: d_eps_out overlaps d_shift", fn);
+    }
+    if (C < 8 || C > ofdm::FFT_ANY_MAX) return fail(OFDM_E_UNSUPPORTED, "%s: C=%d out of [8, 8192]", fn, C);
+    if (4 * max_shift > C)
+        return fail(OFDM_E_ARG, "%s: max_shift=%d, the search needs 4 * max_shift <= C=%d", fn, max_shift, C);
+    if (nframes == 0) return OFDM_OK;
+    return hip_check(ofdm::launch_cfo_acquire(F2(d_iq), nframes, S, R, C, cp_len, F2(d_X), max_shift, min_ratio,
+                                              d_eps_in, d_eps_out, d_shift, d_metric, hs(stream)),
+                     "cfo_acquire");
 }
 
 int ofdm_frame_estimate_freq(const ofdm_cf32 *d_Y, long long nframes, int S, int R, int C,

@@ -3,7 +3,8 @@
 // FFT + combine + normalise + rotate in one HBM pass) and the any-C OFDM
 // modulator (k_tx_any: bin placement + backward FFT + peak + scale + cyclic
 // prefix in one HBM pass; ofdm_tx_modulate) and the delay-domain denoising of
-// the workspace estimate (k_denoise_any; every C), for the sizes the
+// the workspace estimate (k_denoise_any; every C) and the integer carrier
+// offset search on the pilot symbol (k_acquire_any; every C), for the sizes the
 // power-of-two kernels (k_fft_rows, the fused C = 1024 / 2048 / 4096
 // receivers) do not cover: 1536 (LTE 15 MHz), 3072, 6144, 600, 1200, odd and
 // prime lengths, 8192 and the small powers of two.  The reference transforms
@@ -484,6 +485,153 @@ k_denoise_any(float2 *__restrict__ Hc, float *__restrict__ P, long long nframes,
     }
 }
 
+// Integer carrier offset from the pilot symbol (ofdm_frame_cfo_acquire,
+// include/ofdm_lsmrc_acquire.h states the definition), any C: one workgroup
+// per frame, the frame's R pilot rows in order of r in groups of G.  A group
+// arrives in registers (prefix skipped, 8 B per lane: rows are only 8-byte
+// aligned when C + cp is odd; prefetched during the previous group's stages)
+// and goes to LDS times e^{-2 pi i e m / C}, m = cp + i: symbol 0 starts at
+// phase 0, and the in-row phase, e m / C turns (up to 2 |e|, and e may carry an
+// integer part already), is reduced modulo one turn in float64 before the f32
+// sincospi.  The stages run forward; a thread owns the bins b = t + j NT and
+// adds Y[r][b+1] conj(Y[r][b]) of every row in order of r: Z needs no atomics.
+// With all R rows in, Z and q[j] = X[j+1] conj(X[j]) go to LDS and wave w
+// takes the shifts d = -D + w, + NW, ...: its lanes stride over j, sum
+// Z[(j + 1 + d) mod C] conj(q[j]) in float64 and meet in a fixed butterfly.
+// One thread then picks the shift, applies the gate and stores.
+constexpr int ACQ_MAX_SHIFT = 64;
+
+__device__ __forceinline__ bool finite_d(double v) {
+    return (__builtin_bit_cast(unsigned long long, v) & 0x7ff0000000000000ull) != 0x7ff0000000000000ull;
+}
+
+template <int CAP, int NT = nt_of(CAP)>
+__global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(wpe_of(CAP), wpe_of(CAP))))
+k_acquire_any(const float2 *__restrict__ iq, long long nframes, int S, int R, int cp, const float2 *__restrict__ X,
+              int D, float min_ratio, const float *eps_in, float *eps_out, int *shift, float *metric, Plan plan) {
+    constexpr int MAXE = CAP / NT, NW = NT / 64;
+    __shared__ float2 x0[CAP], x1[CAP], lo[TLO], hi[THI];
+    __shared__ double ms[2 * ACQ_MAX_SHIFT + 1];
+    static_assert((CAP == 2048 ? 4 : CAP == 4096 ? 2 : 1) *
+                          (sizeof(float2) * (2 * CAP + TLO + THI) + sizeof(double) * (2 * ACQ_MAX_SHIFT + 1)) <=
+                      160 * 1024, "the resident workgroups (resident()) fit the CU's 160 KiB of LDS");
+    const unsigned C = (unsigned)plan.C, G = (unsigned)plan.G, K = C - 1;
+    const unsigned Cp = C + (unsigned)cp;
+    fill_tables<NT>(lo, hi, C);
+    const Tw T{lo, hi};
+    const int ngr = (R + (int)G - 1) / (int)G, nd = 2 * D + 1;
+    const double invC = 1.0 / (double)C;
+    auto rows_in = [&](int g) { return (unsigned)(R - g * (int)G < (int)G ? R - g * (int)G : (int)G); };
+    // the pilot symbol of frame f, rows g G ..., behind their prefix
+    auto rows_at = [&](long long f, int g) { return iq + ((f * S) * R + (long long)g * G) * Cp + cp; };
+    auto eps_of = [&](long long f) {
+        const float e = eps_in ? eps_in[f] : 0.f;
+        return (__builtin_bit_cast(unsigned, e) & 0x7f800000u) == 0x7f800000u ? 0.f : e;
+    };
+    float2 pf[MAXE], acc[MAXE];
+#pragma unroll
+    for (int j = 0; j < MAXE; ++j) acc[j] = float2{0.f, 0.f};
+    long long f = blockIdx.x;
+    int gi = 0;
+    if (f < nframes) load_rows<NT, MAXE>(pf, rows_at(f, 0), Cp, C, plan.dC, rows_in(0));
+    while (f < nframes) {
+        const unsigned n = rows_in(gi);
+        const double e = (double)eps_of(f);
+#pragma unroll
+        for (int i = 0; i < MAXE; ++i) {
+            const unsigned idx = tid_here() + i * NT, g = fdiv(idx, plan.dC);
+            double turns = e * (double)((unsigned)cp + (idx - g * C)) * invC;
+            turns -= __builtin_rint(turns);
+            float sn, cs;
+            sincospif(-2.f * (float)turns, &sn, &cs);
+            x0[idx] = cmul(pf[i], float2{cs, sn});
+        }
+        lds_sync();  // the group and, the first time, the twiddle tables
+        long long fn = f;
+        int gn = gi + 1;
+        if (gn == ngr) {
+            gn = 0;
+            fn = f + gridDim.x;
+        }
+        if (fn < nframes) load_rows<NT, MAXE>(pf, rows_at(fn, gn), Cp, C, plan.dC, rows_in(gn));
+        const float2 *y = run_stages<NT, false>(x0, x1, T, plan, n, plan.ns);
+#pragma unroll
+        for (int j = 0; j < MAXE; ++j) {
+            const unsigned b = tid_here() + j * NT;
+            if (b < C) {
+                const unsigned b1 = b + 1 == C ? 0 : b + 1;
+                for (unsigned g = 0; g < n; ++g) {
+                    const float2 a = y[g * C + b], c = y[g * C + b1];
+                    // c conj(a)
+                    acc[j] = float2{acc[j].x + (c.x * a.x + c.y * a.y), acc[j].y + (c.y * a.x - c.x * a.y)};
+                }
+            }
+        }
+        lds_sync();  // every row of the group is read: both buffers are free
+        if (gn == 0) {  // frame f complete
+#pragma unroll
+            for (int j = 0; j < MAXE; ++j) {
+                const unsigned b = tid_here() + j * NT;
+                if (b < C) x0[b] = acc[j];
+                acc[j] = float2{0.f, 0.f};
+            }
+            for (unsigned j = tid_here(); j + 1 < K; j += NT) {
+                const float2 a = X[j], c = X[j + 1];
+                x1[j] = float2{c.x * a.x + c.y * a.y, c.y * a.x - c.x * a.y};
+            }
+            lds_sync();
+            const unsigned lane = tid_here() & 63u;
+            for (int di = (int)(tid_here() >> 6); di < nd; di += NW) {
+                const int d = di - D;
+                double ar = 0.0, ai = 0.0;
+                for (unsigned j = lane; j + 1 < K; j += 64) {
+                    int zi = (int)j + 1 + d;  // |d| <= C / 4: one wrap either way
+                    if (zi < 0) zi += (int)C;
+                    if (zi >= (int)C) zi -= (int)C;
+                    const float2 z = x0[zi], q = x1[j];
+                    // z conj(q)
+                    ar += (double)z.x * (double)q.x + (double)z.y * (double)q.y;
+                    ai += (double)z.y * (double)q.x - (double)z.x * (double)q.y;
+                }
+#pragma unroll
+                for (int o = 32; o >= 1; o >>= 1) {
+                    ar += __shfl_xor(ar, o, 64);
+                    ai += __shfl_xor(ai, o, 64);
+                }
+                if (lane == 0) ms[di] = __builtin_sqrt(ar * ar + ai * ai);
+            }
+            lds_sync();
+            if (metric)
+                for (int i = (int)tid_here(); i < nd; i += NT) metric[f * nd + i] = (float)ms[i];
+            if (tid_here() == 0) {
+                // d = 0, -1, +1, -2, +2, ...: the first of equal M wins
+                double best = 0.0;
+                int dh = 0;
+                for (int k = 0; k <= D; ++k) {
+                    for (int sg = -1; sg <= (k ? 1 : -1); sg += 2) {
+                        const double m = ms[D + sg * k];
+                        if (finite_d(m) && m > best) {
+                            best = m;
+                            dh = sg * k;
+                        }
+                    }
+                }
+                double runner = 0.0;
+                for (int i = 0; i < nd; ++i) {
+                    const double m = ms[i];
+                    if (i != dh + D && finite_d(m) && m > runner) runner = m;
+                }
+                if (ms[D + dh] < (double)min_ratio * runner) dh = 0;
+                eps_out[f] = (float)(e + (double)dh);
+                if (shift) shift[f] = dh;
+            }
+            // ms and the two buffers are next written behind later barriers
+        }
+        f = fn;
+        gi = gn;
+    }
+}
+
 // The last FFT stage fused with the combine: the stage's butterfly k1 (of
 // cp = C / P; Lp = cp, no output permutation left) yields bins k1 + cp k2,
 // k2 < P, of one row; each is multiplied by its channel estimate (bin-layout
@@ -777,6 +925,17 @@ hipError_t launch_denoise_t(float2 *Hc, float *P, long long nframes, int R, int 
 }
 
 template <int CAP>
+hipError_t launch_acquire_t(const float2 *iq, long long nframes, int S, int R, int cp, const float2 *X, int D,
+                            float min_ratio, const float *eps_in, float *eps_out, int *shift, float *metric,
+                            const Plan &pl, hipStream_t s) {
+    const long long res = resident(CAP);
+    const unsigned grid = (unsigned)(nframes < res ? nframes : res);  // persistent over the frames
+    hipLaunchKernelGGL((k_acquire_any<CAP>), dim3(grid), dim3(nt_of(CAP)), 0, s, iq, nframes, S, R, cp, X, D,
+                       min_ratio, eps_in, eps_out, shift, metric, pl);
+    return hipGetLastError();
+}
+
+template <int CAP>
 hipError_t launch_mrc_t(const float2 *iq, long long nframes, int S, int R, int prefix, const float2 *Hc,
                         const float *P, float2 *out, int mode, const Plan &pl, hipStream_t s) {
     const long long nq = nframes * (S - 1);
@@ -840,6 +999,24 @@ hipError_t launch_denoise_any(float2 *Hc, float *P, long long nframes, int R, in
     case 4096: return fany::launch_denoise_t<4096>(Hc, P, nframes, R, layC, taps_post, taps_pre, pl, s);
     default: return fany::launch_denoise_t<8192>(Hc, P, nframes, R, layC, taps_post, taps_pre, pl, s);
     }
+}
+
+hipError_t launch_cfo_acquire(const float2 *iq, long long nframes, int S, int R, int C, int cp, const float2 *X,
+                              int max_shift, float min_ratio, const float *eps_in, float *eps_out, int *shift,
+                              float *metric, hipStream_t s) {
+    if (nframes <= 0) return hipSuccess;
+    fany::Plan pl;
+    if (!fany::make_plan(C, pl) || S < 1 || R < 1 || cp < 0 || C < 3 || max_shift < 1 ||
+        max_shift > fany::ACQ_MAX_SHIFT || 4 * max_shift > C)
+        return hipErrorInvalidValue;
+#define OFDM_FANY(CAP) \
+    fany::launch_acquire_t<CAP>(iq, nframes, S, R, cp, X, max_shift, min_ratio, eps_in, eps_out, shift, metric, pl, s)
+    switch (fany::cap_of(C)) {
+    case 2048: return OFDM_FANY(2048);
+    case 4096: return OFDM_FANY(4096);
+    default: return OFDM_FANY(8192);
+    }
+#undef OFDM_FANY
 }
 
 hipError_t launch_mrc_any(const float2 *iq, long long nframes, int S, int R, int C, int prefix, const float2 *Hc,

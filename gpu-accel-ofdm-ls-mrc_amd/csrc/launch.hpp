@@ -167,6 +167,15 @@ hipError_t launch_cfo_estimate(const float2 *iq, long long nframes, int S, int R
                                float2 *gamma, float *eps, hipStream_t s);
 hipError_t launch_cfo_derotate(const float2 *in, float2 *out, long long nframes, int S, int R, int C, int cp,
                                const float *eps, hipStream_t s);
+// Integer offset from the pilot symbol (fft_any.hip k_acquire_any;
+// include/ofdm_lsmrc_acquire.h states the definition): eps_out[f] = eps_in[f]
+// (null or non-finite: 0) + the shift in [-max_shift, max_shift] whose pilot
+// differential correlation is largest and passes the min_ratio gate; shift
+// [nframes] and metric [nframes][2 max_shift + 1] may be null; eps_out may be
+// eps_in.  8 <= C <= FFT_ANY_MAX, 1 <= max_shift <= 64, 4 max_shift <= C.
+hipError_t launch_cfo_acquire(const float2 *iq, long long nframes, int S, int R, int C, int cp, const float2 *X,
+                              int max_shift, float min_ratio, const float *eps_in, float *eps_out, int *shift,
+                              float *metric, hipStream_t s);
 
 // Stage-wise operations of the reference's per-stage gpuLS methods (stages.hip).
 // fused time-domain receiver, C = 2048 (frame_td2048.hip); same contracts

@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "../../include/ofdm_lsmrc.h"
+#include "../../include/ofdm_lsmrc_acquire.h"
 #include "launch.hpp"
 
 struct ofdm_pipeline {
@@ -42,7 +43,9 @@ struct ofdm_pipeline {
     int taps_post = 0, taps_pre = 0;  // ofdm_pipeline_set_denoise; taps_post == 0: off
     bool cfo = false;                 // ofdm_pipeline_set_cfo
     int cp_skip = 0;
-    int phase_mod = 0;                // ofdm_pipeline_set_phase_track; 0: off
+    int search = 0;                   // ofdm_pipeline_set_cfo_search; 0: off
+    float search_ratio = 2.f;
+    int phase_mod = 0;               // ofdm_pipeline_set_phase_track; 0: off
     long long chunk = 0;
     size_t ws_bytes = 0, frame_in = 0, frame_out = 0;  // elements
     ofdm_cf32 *X = nullptr;
@@ -276,6 +279,9 @@ int ofdm_pipeline_submit(ofdm_pipeline *p, long long nframes, ofdm_cf32 *out) {
                                       s.f32, p->s_comp);
         if (rc == OFDM_OK)
             rc = ofdm_frame_cfo_estimate(iq, nframes, p->S, p->R, p->C, p->cp, p->cp_skip, nullptr, s.eps, p->s_comp);
+        if (rc == OFDM_OK && p->search > 0)  // the integer part, in place on the slot's offsets
+            rc = ofdm_frame_cfo_acquire(iq, nframes, p->S, p->R, p->C, p->cp, p->X, p->search, p->search_ratio, s.eps,
+                                        s.eps, nullptr, nullptr, p->s_comp);
         if (rc == OFDM_OK && !fused)
             rc = ofdm_frame_cfo_derotate(iq, iq, nframes, p->S, p->R, p->C, p->cp, s.eps, p->s_comp);
         if (rc == OFDM_OK && p->taps_post > 0) {
@@ -381,6 +387,20 @@ int ofdm_pipeline_set_cfo(ofdm_pipeline *p, int on, int cp_skip) {
         if (!s.eps) PL_TRY(hipMalloc(&s.eps, (size_t)p->chunk * sizeof(float)), fn, "hipMalloc(eps slot)");
     p->cfo = true;
     p->cp_skip = cp_skip;
+    return OFDM_OK;
+}
+
+int ofdm_pipeline_set_cfo_search(ofdm_pipeline *p, int max_shift, float min_ratio) {
+    static const char *fn = "ofdm_pipeline_set_cfo_search";
+    if (!p) return err(OFDM_E_ARG, fn, "null pipeline");
+    if (max_shift < 0 || max_shift > OFDM_ACQ_MAX_SHIFT)
+        return err(OFDM_E_ARG, fn, "max_shift out of [0, OFDM_ACQ_MAX_SHIFT]");
+    if (4 * max_shift > p->C) return err(OFDM_E_ARG, fn, "max_shift: the search needs 4 * max_shift <= C");
+    if (!(min_ratio >= 1.f && min_ratio <= 3.402823466e38f))
+        return err(OFDM_E_ARG, fn, "min_ratio: the gate needs a finite ratio >= 1");
+    if (max_shift > 0 && p->C < 8) return err(OFDM_E_UNSUPPORTED, fn, "the search covers C in [8, 8192]");
+    p->search = max_shift;
+    p->search_ratio = min_ratio;
     return OFDM_OK;
 }
 

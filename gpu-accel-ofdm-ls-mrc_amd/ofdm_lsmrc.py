@@ -24,6 +24,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 _LIBSEL = os.environ.get("OFDM_LSMRC_LIB", "")
 LIB_PATH = os.path.join(HERE, "lib", f"libofdm_lsmrc_{_LIBSEL}.so" if _LIBSEL else "libofdm_lsmrc.so")
 HEADER_PATH = os.path.join(os.path.dirname(HERE), "include", "ofdm_lsmrc.h")
+ACQUIRE_HEADER_PATH = os.path.join(os.path.dirname(HERE), "include", "ofdm_lsmrc_acquire.h")
 
 _c = ctypes
 _P = _c.c_void_p
@@ -105,18 +106,32 @@ _SIGS = {
     "ofdm_buffer_hash": (_I, [_P, _c.c_size_t, _P, _P]),
 }
 
+# include/ofdm_lsmrc_acquire.h (the same library; a table of its own, as the
+# header is a header of its own until it is folded into the main one)
+_SIGS_ACQUIRE = {
+    "ofdm_frame_cfo_acquire": (_I, [_P, _LL, _I, _I, _I, _I, _P, _I, _c.c_float, _P, _P, _P, _P, _P]),
+    "ofdm_pipeline_set_cfo_search": (_I, [_P, _I, _c.c_float]),
+}
+ACQ_MAX_SHIFT = 64  # OFDM_ACQ_MAX_SHIFT
+
+
+def _all_sigs():
+    return list(_SIGS.items()) + list(_SIGS_ACQUIRE.items())
+
 _lib = None
 
 
 def build_id():
     """Identity of the product library's build: the first 16 hex digits of
-    a SHA-256 over its sources (csrc/, the Makefile, include/ofdm_lsmrc.h),
-    in sorted order.  PMC profiles record it (scripts/pmc_summary.py) and
-    bench.py attaches a profile's traffic only to the build it measured."""
+    a SHA-256 over its sources (csrc/, the Makefile, include/ofdm_lsmrc.h,
+    include/ofdm_lsmrc_acquire.h), in sorted order.  PMC profiles record it
+    (scripts/pmc_summary.py) and bench.py attaches a profile's traffic only to
+    the build it measured."""
     import hashlib
     h = hashlib.sha256()
     csrc = os.path.join(HERE, "csrc")
-    files = [os.path.join(csrc, f) for f in sorted(os.listdir(csrc))] + [os.path.join(HERE, "Makefile"), HEADER_PATH]
+    files = [os.path.join(csrc, f) for f in sorted(os.listdir(csrc))] + [os.path.join(HERE, "Makefile"), HEADER_PATH,
+                                                                         ACQUIRE_HEADER_PATH]
     for f in files:
         if os.path.isfile(f):
             h.update(os.path.basename(f).encode() + b"\0")
@@ -142,7 +157,7 @@ def lib():
         # in /opt/rocm's and torch would then load a second runtime.
         import torch  # noqa: F401
         L = _c.CDLL(LIB_PATH)
-        for name, (res, args) in _SIGS.items():
+        for name, (res, args) in _all_sigs():
             if _LIBSEL and not hasattr(L, name):
                 continue  # an older variant build (OFDM_LSMRC_LIB): its missing entries fail when called
             fn = getattr(L, name)  # the product library: every entry, or AttributeError here
@@ -159,7 +174,7 @@ def load_library(path):
     (workspace registry, flag epochs, twiddle tables) is its own."""
     import torch  # noqa: F401  (same HIP runtime as torch, see lib())
     L = _c.CDLL(path)
-    for name, (res, args) in _SIGS.items():
+    for name, (res, args) in _all_sigs():
         if hasattr(L, name):
             fn = getattr(L, name)
             fn.restype = res
@@ -470,6 +485,32 @@ def frame_cfo_estimate(iq, prefix, cp_skip=0, eps=None, gamma=None, stream=None)
                                          None if gamma is None else _dptr(gamma, "gamma"), _eps(eps, F),
                                          _stream(stream)), "ofdm_frame_cfo_estimate")
     return eps
+
+
+def frame_cfo_acquire(iq, X, prefix, max_shift, eps=None, min_ratio=2.0, out=None, shift=None, metric=None,
+                      stream=None):
+    """The integer part of every frame's carrier frequency offset from its
+    pilot symbol (include/ofdm_lsmrc_acquire.h): iq (F, S, R, C+prefix), X the
+    K rotated pilots, eps (F,) float32 the fractional estimate (None: 0) ->
+    out (F,) float32 = eps + the shift in [-max_shift, max_shift] whose pilot
+    differential correlation is largest, 0 where it is less than min_ratio
+    times the runner-up.  out=eps works in place.  shift (F,) int32 and metric
+    (F, 2 max_shift + 1) float32, when given, receive the shifts and the
+    ungated correlation magnitudes."""
+    import torch
+    F, S, R, Cp = iq.shape
+    if out is None:
+        out = torch.empty(F, dtype=torch.float32, device=iq.device)
+    if shift is not None and (shift.dtype != torch.int32 or tuple(shift.shape) != (F,)):
+        raise OfdmError(f"shift must be a torch.int32 tensor of shape ({F},)")
+    if metric is not None and (metric.dtype != torch.float32 or tuple(metric.shape) != (F, 2 * max_shift + 1)):
+        raise OfdmError(f"metric must be a torch.float32 tensor of shape ({F}, {2 * max_shift + 1})")
+    opt = lambda t, name: None if t is None or not F else _dptr(t, name)
+    _check(lib().ofdm_frame_cfo_acquire(_dptr(iq, "iq") if F else None, F, S, R, Cp - prefix, prefix, _dptr(X, "X"),
+                                        max_shift, min_ratio, None if eps is None else _eps(eps, F),
+                                        _eps(out, F, "out"), opt(shift, "shift"), opt(metric, "metric"),
+                                        _stream(stream)), "ofdm_frame_cfo_acquire")
+    return out
 
 
 def frame_cfo_derotate(iq, prefix, eps, out=None, stream=None):
@@ -921,6 +962,13 @@ class Pipeline:
         receiver at C = 1024, frame_cfo_derotate on the slot at any other C.
         on=False turns it off again (the default)."""
         _check(lib().ofdm_pipeline_set_cfo(self._h, int(bool(on)), cp_skip), "ofdm_pipeline_set_cfo")
+
+    def set_cfo_search(self, max_shift, min_ratio=2.0):
+        """Later submits that run with set_cfo on also search the integer
+        part of each frame's offset (frame_cfo_acquire, in place on the
+        chunk's estimates) within +-max_shift subcarrier spacings;
+        max_shift = 0 turns it off again (the default)."""
+        _check(lib().ofdm_pipeline_set_cfo_search(self._h, max_shift, min_ratio), "ofdm_pipeline_set_cfo_search")
 
     def set_phase_track(self, modulation):
         """Later submits run frame_phase_track in place on the slot's output

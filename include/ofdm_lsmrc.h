@@ -565,8 +565,10 @@ int ofdm_pipeline_demod_sc16(ofdm_pipeline *p, const ofdm_sc16 *iq, long long nf
  * Not covered: sc16 x CFO in one kernel, fused derotating receivers for other
  *     C, the one-launch demod, ofdm_symbols_demod, the antenna-split partials,
  *     the frequency-domain entries, integer offsets (|eps| >= 0.5: the
- *     estimator cannot see them), returning the pipeline's estimates to the
- *     caller, and the host C++ mirrors (host/). */
+ *     estimator cannot see them; ofdm_lsmrc_acquire.h finds them from the
+ *     pilot symbol: ofdm_frame_cfo_acquire, ofdm_pipeline_set_cfo_search),
+ *     returning the pipeline's estimates to the caller, and the host C++
+ *     mirrors (host/). */
 int ofdm_frame_cfo_estimate(const ofdm_cf32 *d_iq, long long nframes, int S, int R, int C, int cp_len, int cp_skip,
                             ofdm_cf32 *d_gamma, float *d_eps, ofdm_stream_t stream);
 int ofdm_frame_cfo_derotate(const ofdm_cf32 *d_in, ofdm_cf32 *d_out, long long nframes, int S, int R, int C,
