@@ -43,10 +43,13 @@
 //       element, none per bit.  OUT 0: float; OUT 1: signed byte
 //       clamp(rint(llr * llr_scale), -127, 127), round-to-nearest-even, never
 //       -128.  An element whose P or noise_var is not a positive finite
-//       number gets llr = 0 (an erasure) in both formats.
+//       number gets llr = 0 (an erasure) in both formats.  A non-finite Z with
+//       good P and noise_var gives its own element's LLRs by the formulas (NaN
+//       from a NaN); OUT 1 stores a NaN llr as 0, an erasure too (quant8).
 //   k_noise_estimate<BPS>  one workgroup per frame: the mean over the frame's
 //       (s, k) of P |Z - slice(Z)|^2, slice = the nearest constellation point;
-//       elements whose P is 0 or not finite are skipped (0 if none is left).
+//       elements whose P is 0 or not finite are skipped (0 if none is left); a
+//       non-finite Z that is not skipped makes the frame's value non-finite.
 //       Each thread sums its elements in order into eight accumulators, the
 //       workgroup adds them by a fixed tree in LDS: no atomics, the same bits
 //       on every run.
@@ -95,8 +98,11 @@ __device__ __forceinline__ void elem_llr(float2 z, float p, float nvf, float (&l
     }
 }
 
+// A NaN LLR (a non-finite z with good P and noise_var) is an erasure, 0: the
+// max / min below would return their other operand, a confident -127.
 __device__ __forceinline__ unsigned quant8(float llr, float qs) {
-    const float v = __builtin_fminf(__builtin_fmaxf(llr * qs, -127.f), 127.f);
+    const float x = llr * qs;
+    const float v = x == x ? __builtin_fminf(__builtin_fmaxf(x, -127.f), 127.f) : 0.f;
     return (unsigned)(int)__builtin_rintf(v) & 0xffu;
 }
 

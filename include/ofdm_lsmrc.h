@@ -34,6 +34,43 @@
  *   4: any cp_len works) -- and for the pointers an entry's own comment names;
  *   256 bytes for d_ws.  Every other pointer needs the natural alignment of its
  *   element only: 8 bytes for ofdm_cf32 and the 64-bit words, 4 for float.
+ *
+ * Degenerate and non-finite input.  No entry has data-dependent addressing: a
+ * NaN, an Inf, a zero pilot X[k] or an all-zero pilot symbol is ordinary data,
+ * and it changes only the outputs that depend on it (its footprint); every
+ * other output holds the bits it holds without it.  f frame, s symbol (0 the
+ * pilot), r antenna, b bin, j subcarrier (bin j + 1), pos(j) its output column:
+ *   time-domain receivers (ofdm_frame_demod[_ex], _estimate + _combine, the
+ *     _sc16 and _cfo forms, _ls_partial + _mrc_partial + ofdm_mrc_finalize,
+ *     ofdm_symbols_demod): a time sample of a data row (f, s >= 1, r) reaches
+ *     out[f][s-1][*]; one of a pilot row (f, 0, r) reaches out[f][*][*], the
+ *     estimate rows of (f, r) and P[f]; the cyclic prefix is never read.
+ *     X[k] = 0 reaches out[*][*][pos(k)] and the estimate and P at subcarrier
+ *     k of every frame; an all-zero pilot symbol of frame f gives estimate 0,
+ *     P[f] = 0 and out[f] = NaN (0 / 0) -- the cells the downstream stages
+ *     skip.  d_eps[f] reaches frame f alone.
+ *   frequency-domain receivers and the stage entries: Y[f][s >= 1][r][b]
+ *     reaches out[f][s-1][pos(b-1)] alone, Y[f][0][r][b] reaches
+ *     out[f][*][pos(b-1)], Hconj[r][b-1] and P[b-1]; bin 0 reaches nothing.
+ *   ofdm_fft_rows, ofdm_tx_modulate: an element of row i reaches row i (and
+ *     d_peak[i]).  ofdm_zf_detect / _apply: Y[n][r][k] or X[n][u][k] reaches
+ *     out[n][*][k], Wt[u][r][k] reaches out[*][u][k] (detect) or out[*][r][k]
+ *     (apply); ofdm_zf_precoder: H[u][r][k] reaches W[k] and Wt[*][*][k].
+ *   per-frame outputs (ofdm_frame_cfo_estimate, ofdm_frame_cfo_acquire,
+ *     ofdm_frame_noise_estimate, ofdm_frame_phase_track, ofdm_frame_estimate_
+ *     denoise) and the pipeline's chunks: a sample of frame f reaches frame
+ *     f's values alone -- in a pipeline neither the other frames of its chunk
+ *     nor the later chunks that reuse the slot.
+ * Amplitude range: every receiver output is unchanged, bit for bit, when the
+ * IQ is scaled by a power of two (the exported estimate scales by it, P by its
+ * square), as long as P = sum_r |H|^2 and 1 / P are NORMAL floats for every
+ * used bin: the division is a hardware reciprocal (v_rcp_f32), which flushes
+ * a subnormal P or 1 / P, so outside that range a bin's output is 0 or
+ * non-finite where a true division would still answer.  P is a second power
+ * of the FFT bins, themselves up to C times the samples: IQ of unit amplitude
+ * times 2^+-40 is inside the range at every C and R <= 64, and is what the
+ * tests exercise.  The per-frame CFO outputs scale likewise (gamma and the
+ * acquisition metric by the square, eps and the shift not at all).
  */
 #ifndef OFDM_LSMRC_H_
 #define OFDM_LSMRC_H_
@@ -317,15 +354,21 @@ int ofdm_frame_estimate_denoise(void *d_ws, size_t ws_bytes, long long nframes, 
  * QPSK puts the positive axis where its data bit is SET, the complement of
  * the 38.211 bit: there a hard decision llr < 0 means generator bit 0.
  * An element whose P or noise_var is not positive and finite gets llr = 0.
+ * A non-finite Z with good P and noise_var gives that element's own LLRs
+ * from the formulas above (NaN from a NaN; +-Inf and finite values from an
+ * Inf component) and touches no other element.
  *   OFDM_LLR_F32: d_llr holds floats.
  *   OFDM_LLR_I8:  d_llr holds signed bytes clamp(rint(llr * llr_scale), -127,
- *                 127), round-to-nearest-even; -128 is never produced.
+ *                 127), round-to-nearest-even; -128 is never produced; a NaN
+ *                 llr is stored as 0, an erasure.
  * d_llr: nframes*(S-1)*K*bps values, 16-B aligned.
  *
  * ofdm_frame_noise_estimate: decision-directed, per frame,
  *     d_noise_var[f] = mean over (s, k) of P[f][j] |Z - slice(Z)|^2,
  * slice = the nearest point of the constellation; elements whose P is 0 or
- * not finite are skipped.  Z - X has variance sigma^2 / P[j], so this
+ * not finite are skipped.  A non-finite Z at an element that is not skipped
+ * makes d_noise_var[f] non-finite (the demapper then zeroes frame f's LLRs);
+ * the other frames' values do not change.  Z - X has variance sigma^2 / P[j], so this
  * estimates the per-antenna bin noise INCLUDING the LS estimate's own error
  * (about twice sigma^2 with equal-energy pilots and data) -- the quantity the
  * LLR scale needs.  Fixed-order reduction: bit-identical from run to run. */
@@ -534,7 +577,11 @@ int ofdm_pipeline_demod_sc16(ofdm_pipeline *p, const ofdm_sc16 *iq, long long nf
  *     prefix that the previous symbol's echo spoils.  d_gamma (ofdm_cf32
  *     [nframes]) may be null, d_eps may not.  Any 2 <= C <= 8192; only the
  *     first and last cp_len samples of each row are read.  Summed in a fixed
- *     order in float64, no atomics: bit-identical from run to run.
+ *     order in float64, no atomics: bit-identical from run to run.  A NaN
+ *     among the samples read makes d_gamma[f] and d_eps[f] NaN (the *_cfo
+ *     entries then take that frame's eps as 0); an Inf makes d_gamma[f]
+ *     non-finite and d_eps[f] NaN or a meaningless value in (-0.5, 0.5].  The
+ *     other frames' values do not change.
  *     OFDM_E_ARG, before any device work: cp_len < 1, cp_skip outside
  *     [0, cp_len), bad geometry as in the other frame entries, a null pointer
  *     with nframes > 0.  nframes == 0 is a no-op.

@@ -32,6 +32,7 @@ import functools
 import numpy as np
 import pytest
 
+from denoise_cases import ref_denoise  # the float64 statement
 from helpers import RTOL, parity
 
 pytestmark = pytest.mark.gpu
@@ -77,19 +78,6 @@ def make_frames(F, S, R, C, cp, L, shift=0, sigma=0.05, seed=0):
     iq = np.ascontiguousarray(iq.astype(np.complex64))
     iq.setflags(write=False)
     return iq, X, H, data
-
-
-def ref_denoise(Hconj, C, tp, tq):
-    """The float64 statement: Hconj (..., R, K) -> (Hconj' (..., R, K), Hsqrd' (..., K))."""
-    Hconj = np.asarray(Hconj, np.complex128)
-    H = np.zeros(Hconj.shape[:-1] + (C,), np.complex128)
-    H[..., 1:] = np.conj(Hconj)
-    H[..., 0] = (H[..., 1] + H[..., C - 1]) / 2
-    g = np.fft.ifft(H, axis=-1)
-    n = np.arange(C)
-    g[..., ~((n < tp) | (n >= C - tq))] = 0
-    Hp = np.fft.fft(g, axis=-1)[..., 1:]
-    return np.conj(Hp), np.sum(np.abs(Hp) ** 2, axis=-2)
 
 
 def ref_mrc(iq, cp, Hconj, P):

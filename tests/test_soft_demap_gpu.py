@@ -26,10 +26,11 @@ import functools
 import numpy as np
 import pytest
 
+from soft_cases import A, llr_bound, out_src, ref_llr, ref_noise_var, ref_slice  # the float64 statement
+
 pytestmark = pytest.mark.gpu
 
 NOISE_STD = 0.05
-A = {2: 1 / np.sqrt(2), 4: 1 / np.sqrt(10), 6: 1 / np.sqrt(42), 8: 1 / np.sqrt(170)}
 
 # (F, S, R, C): path
 SHAPES = {
@@ -45,13 +46,6 @@ TIME_DOMAIN_C = (1024, 1536, 2048, 4096)
 CASES = [(shape, bps) for shape in SHAPES for bps in ((2, 4, 6, 8) if shape[3] in (64, 1024) else (2, 6))]
 
 
-def out_src(K):
-    """subcarrier at output position k (shiftOneRow, odd and even K)"""
-    k = np.arange(K)
-    h, n2 = (K - 1) // 2, (K + 1) // 2
-    return np.where(k < n2, k + h, np.where(k < n2 + h, k - n2, k))
-
-
 def map_38211(bits):
     """bits [..., bps] in {0, 1} -> unit-energy Gray-mapped symbols (3GPP TS 38.211 5.1.3-5.1.6)"""
     bps = bits.shape[-1]
@@ -64,47 +58,6 @@ def map_38211(bits):
         return b[..., 0] * amp
 
     return A[bps] * (axis(s[..., 0::2]) + 1j * axis(s[..., 1::2]))
-
-
-def ref_lambdas(x, bps):
-    a = A[bps]
-    t, out = x, []
-    for i in range(bps // 2):
-        if i:
-            t = 2 * a * 2.0 ** (bps // 2 - 1 - i) - np.abs(t)
-        out.append(4 * a * t)
-    return out
-
-
-def ref_llr(Z, scale, bps):
-    """float64 max-log LLRs [..., bps], bit index fastest; scale broadcasts over Z"""
-    Z = Z.astype(np.complex128)
-    re, im = ref_lambdas(Z.real, bps), ref_lambdas(Z.imag, bps)
-    out = np.empty(Z.shape + (bps,))
-    for i in range(bps // 2):
-        out[..., 2 * i] = scale * re[i]
-        out[..., 2 * i + 1] = scale * im[i]
-    return out
-
-
-def ref_slice(Z, bps):
-    a, L = A[bps], 2 ** (bps // 2 - 1)
-
-    def axis(x):
-        return (2 * np.clip(np.floor(x / (2 * a)), -L, L - 1) + 1) * a
-
-    return axis(Z.real) + 1j * axis(Z.imag)
-
-
-def ref_noise_var(Z, Pk, bps):
-    """[F]: mean over (s, k) of P |Z - slice(Z)|^2; Pk [F, 1, K] in output order"""
-    Z = Z.astype(np.complex128)
-    return np.mean(Pk * np.abs(Z - ref_slice(Z, bps)) ** 2, axis=(1, 2))
-
-
-def llr_bound(Z, scale):
-    Z = Z.astype(np.complex128)
-    return (1e-5 * scale * (np.abs(Z.real) + np.abs(Z.imag) + 1))[..., None]
 
 
 def make_frames(F, S, R, C, bps, seed=0):
