@@ -13,6 +13,7 @@
 
 #include "../../include/ofdm_lsmrc.h"
 #include "../../include/ofdm_lsmrc_acquire.h"
+#include "../../include/ofdm_lsmrc_timing.h"
 #include "launch.hpp"
 
 namespace {
@@ -1071,6 +1072,48 @@ int ofdm_frame_phase_track(const ofdm_cf32 *d_z, long long nframes, int S, int R
     Workspace w;
     if ((rc = carve(const_cast<void *>(d_ws), ws_bytes_, nframes, S, R, C, !fused_c(C), w))) return rc;
     return hip_check(ofdm::launch_phase_track(F2(d_z), nframes, S, C, w.P, modulation, F2(d_out), d_phase, hs(stream)),
+                     fn);
+}
+
+// Phase and timing tracking (include/ofdm_lsmrc_timing.h): ofdm_frame_phase_track's
+// rules, with one more optional output.
+int ofdm_frame_timing_track(const ofdm_cf32 *d_z, long long nframes, int S, int R, int C, const void *d_ws,
+                            size_t ws_bytes_, int modulation, ofdm_cf32 *d_out, float *d_phase, float *d_timing,
+                            ofdm_stream_t stream) {
+    static const char *fn = "ofdm_frame_timing_track";
+    if (modulation != OFDM_MOD_QPSK && modulation != OFDM_MOD_QAM16 && modulation != OFDM_MOD_QAM64 &&
+        modulation != OFDM_MOD_QAM256)
+        return fail(OFDM_E_ARG, "%s: modulation=%d (OFDM_MOD_QPSK 2, _QAM16 4, _QAM64 6 or _QAM256 8)", fn, modulation);
+    if (nframes < 0) return fail(OFDM_E_ARG, "%s: nframes < 0", fn);
+    if (S < 2) return fail(OFDM_E_ARG, "%s: S=%d, a frame needs a pilot and >= 1 data symbol", fn, S);
+    if (R < 1) return fail(OFDM_E_ARG, "%s: R=%d < 1", fn, R);
+    if (!valid_c(C)) return fail(OFDM_E_UNSUPPORTED, "%s: C=%d out of [2, 8192]", fn, C);
+    if (nframes == 0) return OFDM_OK;
+    if (!d_z) return fail(OFDM_E_ARG, "%s: null d_z", fn);
+    if (!d_out) return fail(OFDM_E_ARG, "%s: null d_out", fn);
+    if (!d_ws) return fail(OFDM_E_ARG, "%s: null d_ws", fn);
+    if (!aligned(d_z, 8)) return fail(OFDM_E_ARG, "%s: d_z must be 8-byte aligned", fn);
+    if (!aligned(d_out, 8)) return fail(OFDM_E_ARG, "%s: d_out must be 8-byte aligned", fn);
+    if (!aligned(d_phase, 4)) return fail(OFDM_E_ARG, "%s: d_phase must be 4-byte aligned", fn);
+    if (!aligned(d_timing, 4)) return fail(OFDM_E_ARG, "%s: d_timing must be 4-byte aligned", fn);
+    const uintptr_t a = reinterpret_cast<uintptr_t>(d_z), b = reinterpret_cast<uintptr_t>(d_out);
+    const uintptr_t bytes = (uintptr_t)nframes * (S - 1) * (C - 1) * sizeof(ofdm_cf32);
+    const uintptr_t pb = (uintptr_t)nframes * (S - 1) * sizeof(float);
+    if (a != b && a < b + bytes && b < a + bytes)
+        return fail(OFDM_E_ARG, "%s: d_out overlaps d_z (in place, d_out == d_z, or disjoint)", fn);
+    const uintptr_t p = reinterpret_cast<uintptr_t>(d_phase), t = reinterpret_cast<uintptr_t>(d_timing);
+    if (d_phase && ((p < a + bytes && a < p + pb) || (p < b + bytes && b < p + pb)))
+        return fail(OFDM_E_ARG, "%s: d_phase overlaps d_z or d_out", fn);
+    if (d_timing && ((t < a + bytes && a < t + pb) || (t < b + bytes && b < t + pb)))
+        return fail(OFDM_E_ARG, "%s: d_timing overlaps d_z or d_out", fn);
+    if (d_timing && d_phase && t < p + pb && p < t + pb)
+        return fail(OFDM_E_ARG, "%s: d_timing overlaps d_phase", fn);
+    int rc = ws_check(d_ws, ws_bytes_, nframes, S, R, C, true, fn);
+    if (rc) return rc;
+    Workspace w;
+    if ((rc = carve(const_cast<void *>(d_ws), ws_bytes_, nframes, S, R, C, !fused_c(C), w))) return rc;
+    return hip_check(ofdm::launch_timing_track(F2(d_z), nframes, S, C, w.P, modulation, F2(d_out), d_phase, d_timing,
+                                               hs(stream)),
                      fn);
 }
 

@@ -237,6 +237,12 @@ hipError_t launch_soft_demap(const float2 *z, long long nframes, int S, int C, c
 hipError_t launch_phase_track(const float2 *z, long long nframes, int S, int C, const float *P, int bps, float2 *out,
                               float *phase, hipStream_t s);
 
+// Decision-directed phase and timing tracking (timing_track.hip states the
+// recursion, include/ofdm_lsmrc_timing.h the definition).  Arguments as
+// launch_phase_track's; timing: [nframes][S-1] samples (may be null).
+hipError_t launch_timing_track(const float2 *z, long long nframes, int S, int C, const float *P, int bps, float2 *out,
+                               float *phase, float *timing, hipStream_t s);
+
 // OFDM modulator (tx_mod.hip; any C but 1024: fft_any.hip k_tx_any): row i =
 // X + i*ldx (K values, through the bin placement `map`) -> backward FFT ->
 // iq + i*(C+cp): the last cp samples, then the C samples, times 1/peak

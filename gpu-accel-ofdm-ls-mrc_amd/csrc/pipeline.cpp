@@ -24,6 +24,7 @@
 
 #include "../../include/ofdm_lsmrc.h"
 #include "../../include/ofdm_lsmrc_acquire.h"
+#include "../../include/ofdm_lsmrc_timing.h"
 #include "launch.hpp"
 
 struct ofdm_pipeline {
@@ -46,6 +47,7 @@ struct ofdm_pipeline {
     int search = 0;                   // ofdm_pipeline_set_cfo_search; 0: off
     float search_ratio = 2.f;
     int phase_mod = 0;               // ofdm_pipeline_set_phase_track; 0: off
+    int timing_mod = 0;              // ofdm_pipeline_set_timing_track; 0: off; set: runs instead of the phase tracker
     long long chunk = 0;
     size_t ws_bytes = 0, frame_in = 0, frame_out = 0;  // elements
     ofdm_cf32 *X = nullptr;
@@ -339,7 +341,12 @@ int ofdm_pipeline_submit(ofdm_pipeline *p, long long nframes, ofdm_cf32 *out) {
         }
         if (rc) return rc;
     }
-    if (nframes > 0 && p->phase_mod) {
+    if (nframes > 0 && p->timing_mod) {
+        // contains the phase tracker: it runs in its place, not before it
+        int rc = ofdm_frame_timing_track(s.out, nframes, p->S, p->R, p->C, s.ws, p->ws_bytes, p->timing_mod, s.out,
+                                         nullptr, nullptr, p->s_comp);
+        if (rc) return rc;
+    } else if (nframes > 0 && p->phase_mod) {
         // whichever receiver form ran above left its estimate in the slot's workspace
         int rc = ofdm_frame_phase_track(s.out, nframes, p->S, p->R, p->C, s.ws, p->ws_bytes, p->phase_mod, s.out, nullptr,
                                         p->s_comp);
@@ -411,6 +418,16 @@ int ofdm_pipeline_set_phase_track(ofdm_pipeline *p, int modulation) {
         modulation != OFDM_MOD_QAM256)
         return err(OFDM_E_ARG, fn, "modulation must be 0 (off), 2, 4, 6 or 8");
     p->phase_mod = modulation;
+    return OFDM_OK;
+}
+
+int ofdm_pipeline_set_timing_track(ofdm_pipeline *p, int modulation) {
+    static const char *fn = "ofdm_pipeline_set_timing_track";
+    if (!p) return err(OFDM_E_ARG, fn, "null pipeline");
+    if (modulation != 0 && modulation != OFDM_MOD_QPSK && modulation != OFDM_MOD_QAM16 && modulation != OFDM_MOD_QAM64 &&
+        modulation != OFDM_MOD_QAM256)
+        return err(OFDM_E_ARG, fn, "modulation must be 0 (off), 2, 4, 6 or 8");
+    p->timing_mod = modulation;
     return OFDM_OK;
 }
 

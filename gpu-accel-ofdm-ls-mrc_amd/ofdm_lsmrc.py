@@ -25,6 +25,7 @@ _LIBSEL = os.environ.get("OFDM_LSMRC_LIB", "")
 LIB_PATH = os.path.join(HERE, "lib", f"libofdm_lsmrc_{_LIBSEL}.so" if _LIBSEL else "libofdm_lsmrc.so")
 HEADER_PATH = os.path.join(os.path.dirname(HERE), "include", "ofdm_lsmrc.h")
 ACQUIRE_HEADER_PATH = os.path.join(os.path.dirname(HERE), "include", "ofdm_lsmrc_acquire.h")
+TIMING_HEADER_PATH = os.path.join(os.path.dirname(HERE), "include", "ofdm_lsmrc_timing.h")
 
 _c = ctypes
 _P = _c.c_void_p
@@ -114,9 +115,15 @@ _SIGS_ACQUIRE = {
 }
 ACQ_MAX_SHIFT = 64  # OFDM_ACQ_MAX_SHIFT
 
+# include/ofdm_lsmrc_timing.h (likewise)
+_SIGS_TIMING = {
+    "ofdm_frame_timing_track": (_I, [_P, _LL, _I, _I, _I, _P, _c.c_size_t, _I, _P, _P, _P, _P]),
+    "ofdm_pipeline_set_timing_track": (_I, [_P, _I]),
+}
+
 
 def _all_sigs():
-    return list(_SIGS.items()) + list(_SIGS_ACQUIRE.items())
+    return list(_SIGS.items()) + list(_SIGS_ACQUIRE.items()) + list(_SIGS_TIMING.items())
 
 _lib = None
 
@@ -124,14 +131,14 @@ _lib = None
 def build_id():
     """Identity of the product library's build: the first 16 hex digits of
     a SHA-256 over its sources (csrc/, the Makefile, include/ofdm_lsmrc.h,
-    include/ofdm_lsmrc_acquire.h), in sorted order.  PMC profiles record it
+    include/ofdm_lsmrc_acquire.h, include/ofdm_lsmrc_timing.h), in sorted order.  PMC profiles record it
     (scripts/pmc_summary.py) and bench.py attaches a profile's traffic only to
     the build it measured."""
     import hashlib
     h = hashlib.sha256()
     csrc = os.path.join(HERE, "csrc")
     files = [os.path.join(csrc, f) for f in sorted(os.listdir(csrc))] + [os.path.join(HERE, "Makefile"), HEADER_PATH,
-                                                                         ACQUIRE_HEADER_PATH]
+                                                                         ACQUIRE_HEADER_PATH, TIMING_HEADER_PATH]
     for f in files:
         if os.path.isfile(f):
             h.update(os.path.basename(f).encode() + b"\0")
@@ -732,6 +739,44 @@ def residual_cfo(phase, C, prefix):
     return (phase.to(torch.float64) * n).sum(-1) / (n * n).sum() * k
 
 
+def frame_timing_track(z, ws, F, S, R, C, modulation, out=None, phase=None, timing=None, stream=None):
+    """Decision-directed tracking of the common phase and the timing drift of
+    the demodulated symbols z (F, S-1, K) -> the corrected (F, S-1, K); out=z
+    works in place.  P comes from the estimate in ws, as for
+    frame_phase_track.  phase and timing (F, S-1) float32, when given, receive
+    every data symbol's tracked phase (radians, unwrapped) and window offset
+    against the pilot's (samples) (include/ofdm_lsmrc_timing.h)."""
+    import torch
+    if out is None:
+        out = c64((F, S - 1, C - 1), z.device)
+    for name, t in (("phase", phase), ("timing", timing)):
+        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.float32
+                              or tuple(t.shape) != (F, S - 1)):
+            raise OfdmError(f"{name} must be a torch.float32 tensor of shape ({F}, {S - 1})")
+    _check(lib().ofdm_frame_timing_track(_dptr(z, "z") if F else None, F, S, R, C, _dptr(ws, "ws") if F else None,
+                                         ws.numel() if F else 0, modulation, _dptr(out, "out") if F else None,
+                                         _dptr(phase, "phase") if F and phase is not None else None,
+                                         _dptr(timing, "timing") if F and timing is not None else None,
+                                         _stream(stream)),
+           "ofdm_frame_timing_track")
+    return out
+
+
+def sampling_offset(timing, C, prefix):
+    """The sampling clock offset a frame's tracked timing shows, per frame, as
+    a fraction (1e-6 is one ppm): the least-squares slope through the origin
+    of tau over n' = 1 .. S-1 (the pilot is offset 0), sum n' tau / sum n'^2,
+    in samples per symbol, over the C + prefix samples of a symbol.  timing:
+    (F, S-1) torch tensor or numpy array, as frame_timing_track wrote it; the
+    result is of the same kind, float64.  The twin of residual_cfo.  No kernel."""
+    if isinstance(timing, np.ndarray):
+        n = np.arange(1, timing.shape[-1] + 1, dtype=np.float64)
+        return (timing.astype(np.float64) * n).sum(-1) / (n * n).sum() / (C + prefix)
+    import torch
+    n = torch.arange(1, timing.shape[-1] + 1, dtype=torch.float64, device=timing.device)
+    return (timing.to(torch.float64) * n).sum(-1) / (n * n).sum() / (C + prefix)
+
+
 def synth_frames(F, S, R, C, X, prefix=0, seed=1234, frame0=0, noise_std=0.01,
                  freq_domain=False, r0=0, out=None, stream=None):
     Cp = C if freq_domain else C + prefix
@@ -975,6 +1020,12 @@ class Pipeline:
         (modulation 2, 4, 6 or 8), after whichever receiver form the submit
         used and before the copy-out; 0 turns it off again (the default)."""
         _check(lib().ofdm_pipeline_set_phase_track(self._h, modulation), "ofdm_pipeline_set_phase_track")
+
+    def set_timing_track(self, modulation):
+        """Later submits run frame_timing_track in place on the slot's output
+        (modulation 2, 4, 6 or 8), instead of the phase tracker when both are
+        set; 0 turns it off (include/ofdm_lsmrc_timing.h)."""
+        _check(lib().ofdm_pipeline_set_timing_track(self._h, modulation), "ofdm_pipeline_set_timing_track")
 
     def close(self):
         if getattr(self, "_h", None):
