@@ -36,6 +36,7 @@
 // CU), 8192 (512 threads, 128 KiB, 1 per CU); each thread holds CAP / NT
 // elements of a prefetched row group.
 #include "common.hpp"
+#include "fft_any_plan.hpp"
 #include "lane_layout.hpp"
 #include "launch.hpp"
 #include "pk.hpp"
@@ -52,38 +53,20 @@ __device__ __forceinline__ unsigned tid_here() {
     return r;
 }
 
-constexpr int MAX_STAGES = 16;
 constexpr int TLO = 64;          // low twiddle table: W_C^j, j < 64
 constexpr int THI = 8192 / TLO;  // high table: W_C^{64 k}, k < C / 64
 
-// n / d for n < 2^24 as (umulhi(n, m) + n) >> l (round-up magic numbers,
-// computed on the host: the stages divide by runtime sizes per butterfly)
-struct FDiv {
-    unsigned m, l;
-};
+static_assert(PLAN_MAX_C == FFT_ANY_MAX, "the planner's length limit is the library's");
+
+// n / d for n < 2^24 from the planner's magic numbers (fft_any_plan.hpp)
 __device__ __forceinline__ unsigned fdiv(unsigned n, FDiv f) { return (__umulhi(n, f.m) + n) >> f.l; }
-inline FDiv make_fdiv(unsigned d) {
-    const unsigned l = d > 1 ? 32 - __builtin_clz(d - 1) : 0;
-    return FDiv{(unsigned)((((1ull << 32) * ((1ull << l) - d)) / d) + 1), l};
-}
 
 struct Stage {
     int p;
     FDiv cp, Lp, L;  // divisors of the stage: C / p, the product of the earlier radices, Lp * p
 };
-// flat arrays (read by a runtime stage index straight from the kernel
-// arguments; an array of structs would be copied to scratch)
-struct Plan {
-    int C, G, ns;
-    FDiv dC;
-    int p[MAX_STAGES];
-    unsigned m[3][MAX_STAGES], l[3][MAX_STAGES];
-};
 
-// LDS capacity (complex elements per buffer) of the variant that takes C,
-// its threads per workgroup and the waves per SIMD it is built for
-constexpr int cap_of(int C) { return C <= 2048 ? 2048 : C <= 4096 ? 4096 : 8192; }
-constexpr int nt_of(int cap) { return cap <= 4096 ? 256 : 512; }
+// the waves per SIMD a variant (cap_of, nt_of: fft_any_plan.hpp) is built for
 constexpr int wpe_of(int cap) { return cap <= 2048 ? 4 : 2; }
 // the fused MRC holds three prefetch / accumulator arrays beside the stages
 constexpr int wpe_mrc(int cap) { return cap <= 2048 ? 3 : 2; }
@@ -745,7 +728,9 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(wpe_mrc
 k_mrc_any(const float2 *__restrict__ iq, long long nframes, int S, int R, int prefix, const float2 *__restrict__ Hc,
           const float *__restrict__ P, float2 *__restrict__ out, int mode, Plan plan) {
     constexpr int MAXE = CAP / NT;
-    constexpr int NACC = MAXE + 8;  // bins per thread: ceil(C/P / NT) * P <= MAXE + P - 1
+    // bins per thread: ceil(C/P / NT) butterflies of P bins fit the NACC / P slots of every length
+    // (tests/test_any_c_plan_cpu.py::test_accumulator_slots_hold_every_last_stage asserts it for C = 2 ... 8192)
+    constexpr int NACC = MAXE + 8;
     __shared__ float2 x0[CAP], x1[CAP], lo[TLO], hi[THI];
     const unsigned C = (unsigned)plan.C, G = (unsigned)plan.G, K = C - 1;
     const unsigned Cp = C + (unsigned)prefix;
@@ -791,6 +776,7 @@ k_mrc_any(const float2 *__restrict__ iq, long long nframes, int S, int R, int pr
         case 4: last_mac<4, NT>(y, T, Cl, n, H, acc); break;
         case 5: last_mac<5, NT>(y, T, Cl, n, H, acc); break;
         case 7: last_mac<7, NT>(y, T, Cl, n, H, acc); break;
+        // never taken: no plan ends in 8 (tests/test_any_c_plan_cpu.py::test_last_radix_is_never_8)
         case 8: last_mac<8, NT>(y, T, Cl, n, H, acc); break;
         default: last_mac_any<NT>(y, T, Cl, n, (unsigned)pl, H, acc); break;
         }
@@ -811,6 +797,7 @@ k_mrc_any(const float2 *__restrict__ iq, long long nframes, int S, int R, int pr
             case 4: store_acc<4, NT>(acc, o, Pf, Cs, mode); break;
             case 5: store_acc<5, NT>(acc, o, Pf, Cs, mode); break;
             case 7: store_acc<7, NT>(acc, o, Pf, Cs, mode); break;
+            // never taken, as above (test_last_radix_is_never_8)
             case 8: store_acc<8, NT>(acc, o, Pf, Cs, mode); break;
             default: store_acc<0, NT>(acc, o, Pf, Cs, mode); break;
             }
@@ -820,62 +807,6 @@ k_mrc_any(const float2 *__restrict__ iq, long long nframes, int S, int R, int pr
         s = sn;
         gi = gn;
     }
-}
-
-// Radices in stage order: primes above 8 first (their direct stages are
-// the slowest; never the fused last stage), then 8s, 7, 5, 4, 3, 2 -- the
-// smallest last, so that the fused last stage of k_mrc_any has the most
-// butterflies (C / p_last) to spread over the threads; a pure power of 8
-// ends in 4 x 2 instead of 8 for the same reason.
-bool make_plan(int C, Plan &pl) {
-    if (C < 2 || C > FFT_ANY_MAX) return false;
-    pl.C = C;
-    pl.G = cap_of(C) / C;
-    pl.ns = 0;
-    pl.dC = make_fdiv((unsigned)C);
-    int f[32], nf = 0, n = C;
-    int c2 = 0, c3 = 0, c5 = 0, c7 = 0;
-    while (n % 2 == 0) { n /= 2; ++c2; }
-    while (n % 3 == 0) { n /= 3; ++c3; }
-    while (n % 5 == 0) { n /= 5; ++c5; }
-    while (n % 7 == 0) { n /= 7; ++c7; }
-    int big[16], nbig = 0;  // prime factors above 7
-    for (int p = 11; n > 1; p += 2) {
-        if (p * p > n) p = n;
-        while (n % p == 0) {
-            if (nbig == 16) return false;
-            big[nbig++] = p;
-            n /= p;
-        }
-    }
-    for (int i = 0; i < nbig; ++i) f[nf++] = big[i];
-    int tail2 = 0;  // radices 4 / 2 that follow the 8s
-    if (c2 % 3 == 0 && c2 > 0 && c3 + c5 + c7 == 0) {  // pure power of 8 beside primes > 8 only
-        for (int i = 0; i < c2 / 3 - 1; ++i) f[nf++] = 8;
-        tail2 = 3;
-    } else {
-        for (int i = 0; i < c2 / 3; ++i) f[nf++] = 8;
-        tail2 = c2 % 3;
-    }
-    for (int i = 0; i < c7; ++i) f[nf++] = 7;
-    for (int i = 0; i < c5; ++i) f[nf++] = 5;
-    if (tail2 == 2) f[nf++] = 4;
-    if (tail2 == 3) f[nf++] = 4;
-    for (int i = 0; i < c3; ++i) f[nf++] = 3;
-    if (tail2 == 1 || tail2 == 3) f[nf++] = 2;
-    if (nf > MAX_STAGES) return false;
-    int Lp = 1;
-    for (int i = 0; i < nf; ++i) {
-        const int p = f[i];
-        const FDiv d[3] = {make_fdiv((unsigned)(C / p)), make_fdiv((unsigned)Lp), make_fdiv((unsigned)(Lp * p))};
-        for (int k = 0; k < 3; ++k) {
-            pl.m[k][pl.ns] = d[k].m;
-            pl.l[k][pl.ns] = d[k].l;
-        }
-        pl.p[pl.ns++] = p;
-        Lp *= p;
-    }
-    return true;
 }
 
 // resident workgroups of a variant (LDS and registers): 4 per CU at CAP 2048,

@@ -117,6 +117,10 @@ def test_stages_any_c_vs_oracle(ofdm, oracle, dev, C, R):
 
 @pytest.mark.parametrize("C,R,prefix", [(128, 7, 9), (256, 10, 18), (512, 7, 36), (1536, 6, 16), (3072, 5, 24), (6144, 4, 40), (1200, 3, 0)])
 def test_estimate_export_and_antenna_partials_any_c(ofdm, oracle, dev, C, R, prefix):
+    check_export_and_antenna_partials(ofdm, oracle, dev, C, R, prefix)
+
+
+def check_export_and_antenna_partials(ofdm, oracle, dev, C, R, prefix):
     """The estimate of a non-fused size (C = 128 ... 6144: the lane orders of
     frame_td_fft512.hip; 1200: the bin layout) exported to the reference layout
     matches the oracle's LS; the antenna-split partials (numerators + |H|^2)

@@ -66,7 +66,10 @@ PARITY = [(6, 3, 4, 1024, 16, 16),
           (3, 2, 17, 1024, 16, 4),    # more rows than one LDS group holds
           (3, 2, 5, 2048, 0, 8),      # cp = 0, d_eps_in null, integer offsets only
           (2, 2, 2, 8192, 16, 32),
-          (2, 2, 1, 64, 8, 4)]
+          (2, 2, 1, 64, 8, 4),
+          # any_c_cases.CALLER_LENGTHS: 7 * 7, and a prime above 8, a 7 and a 5 in one plan per capacity
+          # (48 bins at C = 49: eight antennas for the model's margin of 3)
+          (4, 2, 8, 49, 5, 8), (4, 2, 3, 770, 9, 16), (3, 2, 2, 2310, 16, 16), (2, 2, 2, 8190, 16, 32)]
 NAN_FRAME = 0  # its offset is an integer: with eps_in acting as 0 nothing fractional is left in the frame
 
 _cases = {}

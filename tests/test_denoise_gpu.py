@@ -32,6 +32,7 @@ import functools
 import numpy as np
 import pytest
 
+from any_c_cases import CALLER_LENGTHS
 from denoise_cases import ref_denoise  # the float64 statement
 from helpers import RTOL, parity
 
@@ -166,7 +167,7 @@ def test_c1024_bin_layout(ofdm, dev, window):
 @pytest.mark.parametrize("C,L,window", [
     (256, 8, (12, 4)), (1536, 16, (24, 8)), (2048, 16, (24, 8)), (4096, 16, (24, 8)),   # each lane order
     (600, 12, (16, 4)), (7, 2, (3, 1)), (4, 2, (2, 1)),                                 # bin layout: mixed radix, prime, tiny
-])
+] + [(C, 12, (16, 4)) for C in CALLER_LENGTHS])  # a prime above 8, a 7 and a 5 in one plan per capacity; 7 * 7
 def test_other_c(ofdm, dev, C, L, window):
     tp, tq = window
     check_denoise(ofdm, dev, 2, 2, 3, C, min(5, C), L, tp, tq, shift=min(tq, 3))

@@ -23,6 +23,7 @@ import numpy as np
 import pytest
 
 import tx_cases
+from any_c_cases import CALLER_LENGTHS
 from helpers import RTOL, parity
 from tx_cases import REF_SHAPES, tx_numpy
 
@@ -76,7 +77,8 @@ def test_c1024_against_statement(ofdm, dev, nrows, cp):
 # K), mixed radices (600 = 8 * 3 * 5^2, 1536 = 2^9 * 3), the three LDS
 # capacities (<= 2048, 4096, 8192).  cp = 5 is beyond C = 2's limit
 # (cp_len <= C): there the largest legal prefix, cp = C, is used.
-@pytest.mark.parametrize("C", [2, 8, 9, 64, 600, 1536, 2048, 4096, 8192])
+# CALLER_LENGTHS: a prime above 8, a 7 and a 5 in one plan per capacity, and 7 * 7.
+@pytest.mark.parametrize("C", [2, 8, 9, 64, 600, 1536, 2048, 4096, 8192] + CALLER_LENGTHS)
 @pytest.mark.parametrize("cp", [0, 5])
 def test_any_c_against_statement(ofdm, dev, C, cp):
     cp = min(cp, C)
