@@ -63,10 +63,18 @@ hipError_t ls_fused(const float2 *iq, long long F, int S, int R, int C, int pref
     if (C == 2048) return ofdm::launch_ls_td2048(iq, F, S, R, prefix, X, Hc, P, partial, s);
     return ofdm::launch_ls_td4096(iq, F, S, R, prefix, X, Hc, P, partial, s);
 }
+// What a pass over a batch of frames computes.  Combine runs against an
+// estimate that exists already (in the workspace, or for ofdm_mrc_demod in
+// the caller's arrays); Full makes it first.
+enum class Pass { LsOnly, Full, Numerator, Combine };
+// the MRC kernels' own `mode`: 0 divides by |H|^2, 1 leaves the numerator
+inline int mrc_mode(Pass p) { return p == Pass::Numerator ? 1 : 0; }
+
 hipError_t tickets_for(unsigned long long *area, hipStream_t s, ofdm::Tickets *tk);
 // tickets: the frame workspace's ticket area (work-ticketed kernels: C = 2048 and 4096)
 hipError_t mrc_fused(const float2 *iq, long long F, int S, int R, int C, int prefix, const float2 *Hc,
-                     const float *P, float2 *out, int mode, hipStream_t s, unsigned long long *tickets) {
+                     const float *P, float2 *out, Pass pass, hipStream_t s, unsigned long long *tickets) {
+    const int mode = mrc_mode(pass);
     if (C == 1024) return ofdm::launch_mrc_td1024(ofdm::iq_f32(iq), F, S, R, prefix, Hc, P, out, mode, s);
     ofdm::Tickets tk;
     if (hipError_t e = tickets_for(tickets, s, &tk); e != hipSuccess) return e;
@@ -192,20 +200,20 @@ hipError_t tickets_for(unsigned long long *area, hipStream_t s, ofdm::Tickets *t
     return hipSuccess;
 }
 
-size_t ws_bytes(long long F, int S, int R, int C, bool need_staging) {
+// the staging buffer belongs to the sizes without a fused receiver
+size_t ws_bytes(long long F, int S, int R, int C) {
     size_t b = up256((size_t)F * R * C * sizeof(float2)) + up256((size_t)F * C * sizeof(float)) +
                up256((size_t)F * sizeof(unsigned long long)) + TICKET_BYTES;
-    if (need_staging) b += up256((size_t)staging_frames(F, S, R, C) * S * R * C * sizeof(float2));
+    if (!fused_c(C)) b += up256((size_t)staging_frames(F, S, R, C) * S * R * C * sizeof(float2));
     return b;
 }
 
-int carve(void *d_ws, size_t bytes, long long F, int S, int R, int C, bool need_staging,
-          Workspace &w) {
-    const size_t need = ws_bytes(F, S, R, C, need_staging);
+int carve(const void *d_ws, size_t bytes, long long F, int S, int R, int C, Workspace &w) {
+    const size_t need = ws_bytes(F, S, R, C);
     if (!d_ws || bytes < need)
         return fail(OFDM_E_ARG, "workspace too small: %zu bytes given, %zu needed", bytes, need);
     if (!aligned(d_ws, 256)) return fail(OFDM_E_ARG, "workspace must be 256-byte aligned");
-    char *p = static_cast<char *>(d_ws);
+    char *p = static_cast<char *>(const_cast<void *>(d_ws));
     w.Hc = reinterpret_cast<float2 *>(p);
     p += up256((size_t)F * R * C * sizeof(float2));
     w.P = reinterpret_cast<float *>(p);
@@ -214,8 +222,8 @@ int carve(void *d_ws, size_t bytes, long long F, int S, int R, int C, bool need_
     p += up256((size_t)F * sizeof(unsigned long long));
     w.tickets = reinterpret_cast<unsigned long long *>(p);
     p += TICKET_BYTES;
-    w.staging = need_staging ? reinterpret_cast<float2 *>(p) : nullptr;
-    w.chunk = need_staging ? staging_frames(F, S, R, C) : F;
+    w.staging = fused_c(C) ? nullptr : reinterpret_cast<float2 *>(p);
+    w.chunk = fused_c(C) ? F : staging_frames(F, S, R, C);
     return OFDM_OK;
 }
 
@@ -250,15 +258,29 @@ void ws_forget(const void *ws) {
     g_ws.erase(ws);
 }
 
-// need_full: the consumer divides by P, so a partial (antenna-split) P is refused
-int ws_check(const void *ws, size_t bytes, long long F, int S, int R, int C, bool need_full, const char *fn,
-             WsTag *out = nullptr) {
+bool ws_lookup(const void *ws, WsTag &tag) {
     std::lock_guard<std::mutex> lock(g_ws_mu);
     auto it = g_ws.find(ws);
-    if (it == g_ws.end())
+    if (it != g_ws.end()) tag = it->second;
+    return it != g_ws.end();
+}
+
+// The estimate layout a consumer takes: the one the receiver of this C
+// writes (lane order where lane_c(C)), the frequency-domain entries' bin
+// layout, or either (the tag says which).
+enum class Layout { Receiver, Freq, Any };
+
+// A consumer opens the workspace an estimate call filled: the registry's
+// entry, its geometry and size against the call's, a full |H|^2 where the
+// consumer divides by it (need_full: an antenna-split partial P is refused),
+// the layout, then the carve.  wrong_layout: what the workspace holds when
+// the layout is not the wanted one, in the entry's words.
+int open_ws(const char *fn, const void *d_ws, size_t bytes, long long F, int S, int R, int C, bool need_full,
+            Layout want, const char *wrong_layout, Workspace &w, WsTag *tag = nullptr) {
+    WsTag t;
+    if (!ws_lookup(d_ws, t))
         return fail(OFDM_E_ARG, "%s: the workspace holds no estimate (run ofdm_frame_estimate, "
                                 "ofdm_frame_demod or ofdm_frame_ls_partial on it first)", fn);
-    const WsTag &t = it->second;
     if (t.F != F || t.S != S || t.R != R || t.C != C)
         return fail(OFDM_E_ARG, "%s: the workspace estimate is for nframes=%lld S=%d R=%d C=%d, "
                                 "called with nframes=%lld S=%d R=%d C=%d", fn, t.F, t.S, t.R, t.C, F, S, R, C);
@@ -267,34 +289,60 @@ int ws_check(const void *ws, size_t bytes, long long F, int S, int R, int C, boo
     if (need_full && t.partial)
         return fail(OFDM_E_ARG, "%s: the workspace holds a partial (antenna-split) |H|^2; "
                                 "finalise with ofdm_mrc_finalize instead", fn);
-    if (out) *out = t;
+    if (want != Layout::Any && t.lane_order != (want == Layout::Receiver && lane_c(C)))
+        return fail(OFDM_E_ARG, "%s: the workspace holds a %s", fn, wrong_layout);
+    if (tag) *tag = t;
+    return carve(d_ws, bytes, F, S, R, C, w);
+}
+
+// ---- argument checks shared by the frame entries: each refusal once ----
+
+int check_frames(const char *fn, long long F, int S, int R) {
+    if (F < 0) return fail(OFDM_E_ARG, "%s: nframes < 0", fn);
+    if (S < 2) return fail(OFDM_E_ARG, "%s: S=%d, a frame needs a pilot and >= 1 data symbol", fn, S);
+    if (R < 1) return fail(OFDM_E_ARG, "%s: R=%d < 1", fn, R);
+    return OFDM_OK;
+}
+
+int check_geometry(const char *fn, long long F, int S, int R, int C) {
+    if (int rc = check_frames(fn, F, S, R)) return rc;
+    if (!valid_c(C)) return fail(OFDM_E_UNSUPPORTED, "%s: C=%d out of [2, 8192]", fn, C);
     return OFDM_OK;
 }
 
 int check_frame_args(const void *in, long long F, int S, int R, int C, int prefix,
                      const void *out, const char *fn) {
-    if (F < 0) return fail(OFDM_E_ARG, "%s: nframes < 0", fn);
     if (F > 0 && (!in || !out)) return fail(OFDM_E_ARG, "%s: null pointer", fn);
-    if (S < 2) return fail(OFDM_E_ARG, "%s: S=%d, a frame needs a pilot and >= 1 data symbol", fn, S);
-    if (R < 1) return fail(OFDM_E_ARG, "%s: R=%d < 1", fn, R);
-    if (!valid_c(C)) return fail(OFDM_E_UNSUPPORTED, "%s: C=%d out of [2, 8192]", fn, C);
+    if (int rc = check_geometry(fn, F, S, R, C)) return rc;
     if (prefix < 0 || prefix > C) return fail(OFDM_E_ARG, "%s: prefix=%d out of [0, C]", fn, prefix);
     if (!aligned(in, 16)) return fail(OFDM_E_ARG, "%s: input must be 16-byte aligned", fn);
     return OFDM_OK;
+}
+
+int check_modulation(const char *fn, int m) {
+    if (m != OFDM_MOD_QPSK && m != OFDM_MOD_QAM16 && m != OFDM_MOD_QAM64 && m != OFDM_MOD_QAM256)
+        return fail(OFDM_E_ARG, "%s: modulation=%d (OFDM_MOD_QPSK 2, _QAM16 4, _QAM64 6 or _QAM256 8)", fn, m);
+    return OFDM_OK;
+}
+
+bool positive_finite(float x) { return x > 0.f && x <= 3.402823466e38f; }
+
+// whether the byte intervals [a, a + na) and [b, b + nb) meet
+bool overlaps(const void *a, uintptr_t na, const void *b, uintptr_t nb) {
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return x < y + nb && y < x + na;
 }
 
 // Generic (non-fused) time-domain frames.  LS: the pilot rows of each chunk
 // of frames FFT'd into the staging buffer (fft_any / k_fft_rows), then the
 // frequency-domain LS kernel (bin-layout Hc, P).  MRC: one fused pass over the
 // IQ (k_mrc_any: FFT + combine + normalise + rotate per symbol in LDS).
-// mode: 0 = full demod, 1 = MRC numerator only, 2 = LS only,
-//       3 = full demod against an estimate already in the workspace
 int td_staged(const float2 *iq, long long F, int S, int R, int C, int prefix, const float2 *X,
-              const Workspace &w, float2 *out, int mode, hipStream_t s) {
+              const Workspace &w, float2 *out, Pass pass, hipStream_t s) {
     const long long frame_in = (long long)S * R * (C + prefix);
     const bool lane512 = ofdm::lane512_supported(C);
     hipError_t e;
-    if (mode == 0 || mode == 2) {
+    if (pass == Pass::Full || pass == Pass::LsOnly) {
         // the staging buffer holds w.chunk whole frames = w.chunk * S frames' pilot rows
         const long long per = w.chunk * S, pilot = (long long)R * C;
         for (long long f0 = 0; f0 < F; f0 += per) {
@@ -308,14 +356,13 @@ int td_staged(const float2 *iq, long long F, int S, int R, int C, int prefix, co
             if (e != hipSuccess) return hip_check(e, "ls_freq");
         }
     }
-    if (mode == 2) return OFDM_OK;
+    if (pass == Pass::LsOnly) return OFDM_OK;
     if (lane512) {
         char what[16];  // the kernel's name in the error text: mrc_td1536 / 3072 / 6144, mrc_small below
         snprintf(what, sizeof what, C < 1024 ? "mrc_small" : "mrc_td%d", C);
-        return hip_check(ofdm::launch_mrc_lane512(C, iq, F, S, R, prefix, w.Hc, w.P, out, mode == 1 ? 1 : 0, s), what);
+        return hip_check(ofdm::launch_mrc_lane512(C, iq, F, S, R, prefix, w.Hc, w.P, out, mrc_mode(pass), s), what);
     }
-    return hip_check(ofdm::launch_mrc_any(iq, F, S, R, C, prefix, w.Hc, w.P, out, mode == 1 ? 1 : 0, s),
-                     "mrc_any");
+    return hip_check(ofdm::launch_mrc_any(iq, F, S, R, C, prefix, w.Hc, w.P, out, mrc_mode(pass), s), "mrc_any");
 }
 
 }  // namespace
@@ -386,16 +433,16 @@ int ofdm_ls_estimate(const ofdm_cf32 *d_Y, const ofdm_cf32 *d_X, int R, int C, o
 }
 
 static int mrc_common(const ofdm_cf32 *d_Y, long long nsyms, const ofdm_cf32 *d_Hconj,
-                      const float *d_Hsqrd, int R, int C, ofdm_cf32 *d_out, int mode,
+                      const float *d_Hsqrd, int R, int C, ofdm_cf32 *d_out, Pass pass,
                       ofdm_stream_t stream, const char *fn) {
-    if (!d_Y || !d_Hconj || !d_out || (mode == 0 && !d_Hsqrd) || R < 1 || nsyms < 0)
+    if (!d_Y || !d_Hconj || !d_out || (pass == Pass::Combine && !d_Hsqrd) || R < 1 || nsyms < 0)
         return fail(OFDM_E_ARG, "%s: bad arguments", fn);
     if (!valid_c(C)) return fail(OFDM_E_UNSUPPORTED, "%s: C=%d out of [2, 8192]", fn, C);
     if (!aligned(d_Y, 16)) return fail(OFDM_E_ARG, "%s: d_Y must be 16-byte aligned", fn);
     const int K = C - 1;
     // all symbols share one estimate: one "frame" holding nsyms data symbols
     return hip_check(ofdm::launch_mrc_freq(F2(d_Y), 0, (long long)R * C, 1, (int)nsyms, R, C,
-                                           F2(d_Hconj), 0, K, 0, d_Hsqrd, 0, 0, F2(d_out), mode,
+                                           F2(d_Hconj), 0, K, 0, d_Hsqrd, 0, 0, F2(d_out), mrc_mode(pass),
                                            hs(stream)),
                      fn);
 }
@@ -403,13 +450,13 @@ static int mrc_common(const ofdm_cf32 *d_Y, long long nsyms, const ofdm_cf32 *d_
 int ofdm_mrc_demod(const ofdm_cf32 *d_Y, long long nsyms, const ofdm_cf32 *d_Hconj,
                    const float *d_Hsqrd, int R, int C, ofdm_cf32 *d_out, ofdm_stream_t stream) {
     if (nsyms > 0x7fffffffll) return fail(OFDM_E_ARG, "ofdm_mrc_demod: nsyms too large");
-    return mrc_common(d_Y, nsyms, d_Hconj, d_Hsqrd, R, C, d_out, 0, stream, "ofdm_mrc_demod");
+    return mrc_common(d_Y, nsyms, d_Hconj, d_Hsqrd, R, C, d_out, Pass::Combine, stream, "ofdm_mrc_demod");
 }
 
 int ofdm_mrc_numerator(const ofdm_cf32 *d_Y, long long nsyms, const ofdm_cf32 *d_Hconj, int R,
                        int C, ofdm_cf32 *d_num, ofdm_stream_t stream) {
     if (nsyms > 0x7fffffffll) return fail(OFDM_E_ARG, "ofdm_mrc_numerator: nsyms too large");
-    return mrc_common(d_Y, nsyms, d_Hconj, nullptr, R, C, d_num, 1, stream, "ofdm_mrc_numerator");
+    return mrc_common(d_Y, nsyms, d_Hconj, nullptr, R, C, d_num, Pass::Numerator, stream, "ofdm_mrc_numerator");
 }
 
 int ofdm_mrc_finalize(const ofdm_cf32 *d_num, long long e0, long long count, int nsym, int K,
@@ -455,7 +502,7 @@ int ofdm_dist_sqrd(const ofdm_cf32 *d_H, int R, int K, float *d_Hsqrd, ofdm_stre
 
 size_t ofdm_frame_workspace_bytes(long long nframes, int S, int R, int C) {
     if (nframes < 0 || S < 2 || R < 1 || !valid_c(C)) return 0;
-    return ws_bytes(nframes, S, R, C, !fused_c(C));
+    return ws_bytes(nframes, S, R, C);
 }
 
 int ofdm_workspace_release(const void *d_ws) {
@@ -477,13 +524,13 @@ int ofdm_frame_estimate(const ofdm_cf32 *d_iq, long long nframes, int S, int R, 
     if (!d_X) return fail(OFDM_E_ARG, "ofdm_frame_estimate: null pilots");
     if (nframes == 0) return OFDM_OK;
     Workspace w;
-    if ((rc = carve(d_ws, ws_bytes_, nframes, S, R, C, !fused_c(C), w))) return rc;
+    if ((rc = carve(d_ws, ws_bytes_, nframes, S, R, C, w))) return rc;
     ws_forget(d_ws);
     hipStream_t s = hs(stream);
     if (fused_c(C))
         rc = hip_check(ls_fused(F2(d_iq), nframes, S, R, C, prefix, F2(d_X), w.Hc, w.P, 0, s), "ls_fused");
     else
-        rc = td_staged(F2(d_iq), nframes, S, R, C, prefix, F2(d_X), w, nullptr, 2, s);
+        rc = td_staged(F2(d_iq), nframes, S, R, C, prefix, F2(d_X), w, nullptr, Pass::LsOnly, s);
     if (rc == OFDM_OK) ws_record(d_ws, ws_bytes_, nframes, S, R, C, lane_c(C), false);
     return rc;
 }
@@ -494,20 +541,17 @@ int ofdm_frame_combine(const ofdm_cf32 *d_iq, long long nframes, int S, int R, i
     int rc = check_frame_args(d_iq, nframes, S, R, C, prefix, d_out, "ofdm_frame_combine");
     if (rc) return rc;
     if (nframes == 0) return OFDM_OK;
-    WsTag tag;
-    if ((rc = ws_check(d_ws, ws_bytes_, nframes, S, R, C, true, "ofdm_frame_combine", &tag))) return rc;
-    if (tag.lane_order != lane_c(C))
-        return fail(OFDM_E_ARG, "ofdm_frame_combine: the workspace holds a frequency-domain estimate "
-                                "(use ofdm_frame_combine_freq)");
     Workspace w;
-    if ((rc = carve(d_ws, ws_bytes_, nframes, S, R, C, !fused_c(C), w))) return rc;
+    if ((rc = open_ws("ofdm_frame_combine", d_ws, ws_bytes_, nframes, S, R, C, true, Layout::Receiver,
+                      "frequency-domain estimate (use ofdm_frame_combine_freq)", w)))
+        return rc;
     hipStream_t s = hs(stream);
     if (fused_c(C))
-        return hip_check(mrc_fused(F2(d_iq), nframes, S, R, C, prefix, w.Hc, w.P,
-                                                 F2(d_out), 0, s, w.tickets),
+        return hip_check(mrc_fused(F2(d_iq), nframes, S, R, C, prefix, w.Hc, w.P, F2(d_out), Pass::Combine, s,
+                                   w.tickets),
                          "mrc_fused");
     // staged path: the FFT of every chunk is redone here (estimate kept only Hc/P)
-    return td_staged(F2(d_iq), nframes, S, R, C, prefix, nullptr, w, F2(d_out), 3, s);
+    return td_staged(F2(d_iq), nframes, S, R, C, prefix, nullptr, w, F2(d_out), Pass::Combine, s);
 }
 
 int ofdm_frame_demod(const ofdm_cf32 *d_iq, long long nframes, int S, int R, int C, int prefix,
@@ -528,7 +572,7 @@ int ofdm_frame_demod_ex(const ofdm_cf32 *d_iq, long long nframes, int S, int R, 
         return fail(OFDM_E_ARG, "ofdm_frame_demod_ex: flow=%d (OFDM_FLOW_AUTO or OFDM_FLOW_TWO_LAUNCH)", flow);
     if (nframes == 0) return OFDM_OK;
     Workspace w;
-    if ((rc = carve(d_ws, ws_bytes_, nframes, S, R, C, !fused_c(C), w))) return rc;
+    if ((rc = carve(d_ws, ws_bytes_, nframes, S, R, C, w))) return rc;
     hipStream_t s = hs(stream);
     ws_forget(d_ws);
     if (flow == OFDM_FLOW_AUTO && one_launch_demod(C, s)) {
@@ -546,72 +590,101 @@ int ofdm_frame_demod_ex(const ofdm_cf32 *d_iq, long long nframes, int S, int R, 
         if (rc) return rc;
         // the estimate is in the workspace once the LS launch is enqueued
         ws_record(d_ws, ws_bytes_, nframes, S, R, C, true, false);
-        return hip_check(mrc_fused(F2(d_iq), nframes, S, R, C, prefix, w.Hc, w.P, F2(d_out), 0, s, w.tickets),
+        return hip_check(mrc_fused(F2(d_iq), nframes, S, R, C, prefix, w.Hc, w.P, F2(d_out), Pass::Combine, s,
+                                   w.tickets),
                          "mrc_fused");
     }
-    rc = td_staged(F2(d_iq), nframes, S, R, C, prefix, F2(d_X), w, F2(d_out), 0, s);
+    rc = td_staged(F2(d_iq), nframes, S, R, C, prefix, F2(d_X), w, F2(d_out), Pass::Full, s);
     if (rc == OFDM_OK) ws_record(d_ws, ws_bytes_, nframes, S, R, C, lane_c(C), false);
     return rc;
 }
 
-// The sc16 and CFO frame entries (C = 1024, two launches) behind their own
-// argument checks: what the fp32 entries do at a fused C, on the entry's
-// sample source.
-static int ls_1024(const ofdm::Iq1024 &src, long long nframes, int S, int R, int prefix, const ofdm_cf32 *d_X,
+// The sc16 and CFO frame entries (C = 1024, two launches): what the fp32
+// entries do at a fused C, on the entry's sample source.  estimate_1024,
+// combine_1024 and demod_1024 are the entries in full: the refusals in the
+// header's order, every one before any HIP call, then the launches.
+static inline const ofdm::sc16 *SC(const ofdm_sc16 *p) { return reinterpret_cast<const ofdm::sc16 *>(p); }
+static_assert(sizeof(ofdm_sc16) == 4 && sizeof(ofdm::sc16) == 4, "one dword per sc16 sample");
+// The entry's kind of source is stated, never read off a pointer: an empty batch may come with null samples.
+struct Source {
+    bool sc16;         // int16 samples and a scale; else fp32 samples and one offset per frame
+    ofdm::Iq1024 iq;
+    const void *samples() const { return sc16 ? (const void *)iq.i16 : (const void *)iq.f32; }
+    const char *kernel(const char *sc16_name, const char *cfo_name) const { return sc16 ? sc16_name : cfo_name; }
+};
+static Source sc16_source(const ofdm_sc16 *d_iq, float scale) { return {true, ofdm::iq_sc16(SC(d_iq), scale)}; }
+static Source cfo_source(const ofdm_cf32 *d_iq, const float *d_eps) { return {false, ofdm::iq_f32(F2(d_iq), d_eps)}; }
+
+// what the source asks after check_frame_args: sc16 a scale, the derotating receiver its offsets
+static int check_source(const char *fn, const Source &src, long long nframes, int C) {
+    if (src.sc16 && !positive_finite(src.iq.scale))
+        return fail(OFDM_E_ARG, "%s: scale=%g, sc16 samples need a positive finite scale", fn, (double)src.iq.scale);
+    if (!src.sc16 && nframes > 0 && !src.iq.eps) return fail(OFDM_E_ARG, "%s: null d_eps", fn);
+    if (C != 1024)
+        return fail(OFDM_E_UNSUPPORTED,
+                    src.sc16 ? "%s: C=%d (the sc16 receiver covers C = 1024; convert with ofdm_iq_convert_sc16 and "
+                               "call the fp32 entry)"
+                             : "%s: C=%d (the derotating receiver covers C = 1024; derotate with "
+                               "ofdm_frame_cfo_derotate and call the fp32 entry)", fn, C);
+    return OFDM_OK;
+}
+static int ls_1024(const Source &src, long long nframes, int S, int R, int prefix, const ofdm_cf32 *d_X,
                    void *d_ws, size_t ws_bytes_, const Workspace &w, hipStream_t s) {
     ws_forget(d_ws);
-    int rc = hip_check(ofdm::launch_ls_td1024(src, nframes, S, R, prefix, F2(d_X), w.Hc, w.P, 0, s),
-                       src.i16 ? "ls_td1024_sc16" : "ls_td1024_cfo");
+    int rc = hip_check(ofdm::launch_ls_td1024(src.iq, nframes, S, R, prefix, F2(d_X), w.Hc, w.P, 0, s),
+                       src.kernel("ls_td1024_sc16", "ls_td1024_cfo"));
     // the estimate is in the workspace once the LS launch is enqueued
     if (rc == OFDM_OK) ws_record(d_ws, ws_bytes_, nframes, S, R, 1024, true, false);
     return rc;
 }
-static int mrc_1024(const ofdm::Iq1024 &src, long long nframes, int S, int R, int prefix, const Workspace &w,
+static int mrc_1024(const Source &src, long long nframes, int S, int R, int prefix, const Workspace &w,
                     ofdm_cf32 *d_out, hipStream_t s) {
-    return hip_check(ofdm::launch_mrc_td1024(src, nframes, S, R, prefix, w.Hc, w.P, F2(d_out), 0, s),
-                     src.i16 ? "mrc_td1024_sc16" : "mrc_td1024_cfo");
+    const int mode = mrc_mode(Pass::Combine);
+    return hip_check(ofdm::launch_mrc_td1024(src.iq, nframes, S, R, prefix, w.Hc, w.P, F2(d_out), mode, s),
+                     src.kernel("mrc_td1024_sc16", "mrc_td1024_cfo"));
 }
-static int estimate_1024(const ofdm::Iq1024 &src, long long nframes, int S, int R, int prefix, const ofdm_cf32 *d_X,
-                         void *d_ws, size_t ws_bytes_, ofdm_stream_t stream) {
+static int estimate_1024(const char *fn, const Source &src, long long nframes, int S, int R, int C, int prefix,
+                         const ofdm_cf32 *d_X, void *d_ws, size_t ws_bytes_, ofdm_stream_t stream) {
+    int rc = check_frame_args(src.samples(), nframes, S, R, C, prefix, d_ws, fn);
+    if (rc) return rc;
+    if ((rc = check_source(fn, src, nframes, C))) return rc;
+    if (!d_X) return fail(OFDM_E_ARG, "%s: null pilots", fn);
+    if (nframes == 0) return OFDM_OK;
     Workspace w;
-    if (int rc = carve(d_ws, ws_bytes_, nframes, S, R, 1024, false, w)) return rc;
+    if ((rc = carve(d_ws, ws_bytes_, nframes, S, R, C, w))) return rc;
     return ls_1024(src, nframes, S, R, prefix, d_X, d_ws, ws_bytes_, w, hs(stream));
 }
-static int combine_1024(const char *fn, const ofdm::Iq1024 &src, long long nframes, int S, int R, int prefix,
+static int combine_1024(const char *fn, const Source &src, long long nframes, int S, int R, int C, int prefix,
                         void *d_ws, size_t ws_bytes_, ofdm_cf32 *d_out, ofdm_stream_t stream) {
-    WsTag tag;
-    if (int rc = ws_check(d_ws, ws_bytes_, nframes, S, R, 1024, true, fn, &tag)) return rc;
-    if (!tag.lane_order)
-        return fail(OFDM_E_ARG, "%s: the workspace holds a frequency-domain estimate (use ofdm_frame_combine_freq)", fn);
+    if (int st = take_status(fn)) return st;
+    int rc = check_frame_args(src.samples(), nframes, S, R, C, prefix, d_out, fn);
+    if (rc) return rc;
+    if ((rc = check_source(fn, src, nframes, C))) return rc;
+    if (nframes == 0) return OFDM_OK;
     Workspace w;
-    if (int rc = carve(d_ws, ws_bytes_, nframes, S, R, 1024, false, w)) return rc;
+    if ((rc = open_ws(fn, d_ws, ws_bytes_, nframes, S, R, C, true, Layout::Receiver,
+                      "frequency-domain estimate (use ofdm_frame_combine_freq)", w)))
+        return rc;
     return mrc_1024(src, nframes, S, R, prefix, w, d_out, hs(stream));
 }
-static int demod_1024(const ofdm::Iq1024 &src, long long nframes, int S, int R, int prefix, const ofdm_cf32 *d_X,
-                      void *d_ws, size_t ws_bytes_, ofdm_cf32 *d_out, ofdm_stream_t stream) {
+static int demod_1024(const char *fn, const Source &src, long long nframes, int S, int R, int C, int prefix,
+                      const ofdm_cf32 *d_X, void *d_ws, size_t ws_bytes_, ofdm_cf32 *d_out, ofdm_stream_t stream) {
+    if (int st = take_status(fn)) return st;
+    int rc = check_frame_args(src.samples(), nframes, S, R, C, prefix, d_out, fn);
+    if (rc) return rc;
+    if ((rc = check_source(fn, src, nframes, C))) return rc;
+    if (!d_X) return fail(OFDM_E_ARG, "%s: null pilots", fn);
+    if (nframes == 0) return OFDM_OK;
     Workspace w;
-    if (int rc = carve(d_ws, ws_bytes_, nframes, S, R, 1024, false, w)) return rc;
-    if (int rc = ls_1024(src, nframes, S, R, prefix, d_X, d_ws, ws_bytes_, w, hs(stream))) return rc;
+    if ((rc = carve(d_ws, ws_bytes_, nframes, S, R, C, w))) return rc;
+    if ((rc = ls_1024(src, nframes, S, R, prefix, d_X, d_ws, ws_bytes_, w, hs(stream)))) return rc;
     return mrc_1024(src, nframes, S, R, prefix, w, d_out, hs(stream));
 }
-
-// sc16 IQ: the checks every sc16 frame entry makes after check_frame_args,
-// before any HIP call.
-static int check_sc16(const char *fn, float scale, int C) {
-    if (!(scale > 0.f && scale <= 3.402823466e38f))
-        return fail(OFDM_E_ARG, "%s: scale=%g, sc16 samples need a positive finite scale", fn, (double)scale);
-    if (C != 1024)
-        return fail(OFDM_E_UNSUPPORTED, "%s: C=%d (the sc16 receiver covers C = 1024; convert with "
-                                        "ofdm_iq_convert_sc16 and call the fp32 entry)", fn, C);
-    return OFDM_OK;
-}
-static inline const ofdm::sc16 *SC(const ofdm_sc16 *p) { return reinterpret_cast<const ofdm::sc16 *>(p); }
-static_assert(sizeof(ofdm_sc16) == 4 && sizeof(ofdm::sc16) == 4, "one dword per sc16 sample");
 
 int ofdm_iq_convert_sc16(const ofdm_sc16 *d_in, long long n, float scale, ofdm_cf32 *d_out, ofdm_stream_t stream) {
     static const char *fn = "ofdm_iq_convert_sc16";
     if (n < 0) return fail(OFDM_E_ARG, "%s: n < 0", fn);
-    if (!(scale > 0.f && scale <= 3.402823466e38f))
+    if (!positive_finite(scale))
         return fail(OFDM_E_ARG, "%s: scale=%g, sc16 samples need a positive finite scale", fn, (double)scale);
     if (n == 0) return OFDM_OK;
     if (!d_in || !d_out) return fail(OFDM_E_ARG, "%s: null pointer", fn);
@@ -621,46 +694,20 @@ int ofdm_iq_convert_sc16(const ofdm_sc16 *d_in, long long n, float scale, ofdm_c
 
 int ofdm_frame_estimate_sc16(const ofdm_sc16 *d_iq, long long nframes, int S, int R, int C, int prefix, float scale,
                              const ofdm_cf32 *d_X, void *d_ws, size_t ws_bytes_, ofdm_stream_t stream) {
-    static const char *fn = "ofdm_frame_estimate_sc16";
-    int rc = check_frame_args(d_iq, nframes, S, R, C, prefix, d_ws, fn);
-    if (rc) return rc;
-    if ((rc = check_sc16(fn, scale, C))) return rc;
-    if (!d_X) return fail(OFDM_E_ARG, "%s: null pilots", fn);
-    if (nframes == 0) return OFDM_OK;
-    return estimate_1024(ofdm::iq_sc16(SC(d_iq), scale), nframes, S, R, prefix, d_X, d_ws, ws_bytes_, stream);
+    return estimate_1024("ofdm_frame_estimate_sc16", sc16_source(d_iq, scale), nframes, S, R, C, prefix, d_X, d_ws,
+                         ws_bytes_, stream);
 }
 
 int ofdm_frame_combine_sc16(const ofdm_sc16 *d_iq, long long nframes, int S, int R, int C, int prefix, float scale,
                             void *d_ws, size_t ws_bytes_, ofdm_cf32 *d_out, ofdm_stream_t stream) {
-    static const char *fn = "ofdm_frame_combine_sc16";
-    if (int st = take_status(fn)) return st;
-    int rc = check_frame_args(d_iq, nframes, S, R, C, prefix, d_out, fn);
-    if (rc) return rc;
-    if ((rc = check_sc16(fn, scale, C))) return rc;
-    if (nframes == 0) return OFDM_OK;
-    return combine_1024(fn, ofdm::iq_sc16(SC(d_iq), scale), nframes, S, R, prefix, d_ws, ws_bytes_, d_out, stream);
+    return combine_1024("ofdm_frame_combine_sc16", sc16_source(d_iq, scale), nframes, S, R, C, prefix, d_ws,
+                        ws_bytes_, d_out, stream);
 }
 
 int ofdm_frame_demod_sc16(const ofdm_sc16 *d_iq, long long nframes, int S, int R, int C, int prefix, float scale,
                           const ofdm_cf32 *d_X, void *d_ws, size_t ws_bytes_, ofdm_cf32 *d_out, ofdm_stream_t stream) {
-    static const char *fn = "ofdm_frame_demod_sc16";
-    if (int st = take_status(fn)) return st;
-    int rc = check_frame_args(d_iq, nframes, S, R, C, prefix, d_out, fn);
-    if (rc) return rc;
-    if ((rc = check_sc16(fn, scale, C))) return rc;
-    if (!d_X) return fail(OFDM_E_ARG, "%s: null pilots", fn);
-    if (nframes == 0) return OFDM_OK;
-    return demod_1024(ofdm::iq_sc16(SC(d_iq), scale), nframes, S, R, prefix, d_X, d_ws, ws_bytes_, d_out, stream);
-}
-
-// Carrier frequency offset: the checks every *_cfo receiver entry makes after
-// check_frame_args, before any HIP call.
-static int check_cfo(const char *fn, long long nframes, const float *d_eps, int C) {
-    if (nframes > 0 && !d_eps) return fail(OFDM_E_ARG, "%s: null d_eps", fn);
-    if (C != 1024)
-        return fail(OFDM_E_UNSUPPORTED, "%s: C=%d (the derotating receiver covers C = 1024; derotate with "
-                                        "ofdm_frame_cfo_derotate and call the fp32 entry)", fn, C);
-    return OFDM_OK;
+    return demod_1024("ofdm_frame_demod_sc16", sc16_source(d_iq, scale), nframes, S, R, C, prefix, d_X, d_ws,
+                      ws_bytes_, d_out, stream);
 }
 
 int ofdm_frame_cfo_estimate(const ofdm_cf32 *d_iq, long long nframes, int S, int R, int C, int cp_len, int cp_skip,
@@ -684,9 +731,8 @@ int ofdm_frame_cfo_derotate(const ofdm_cf32 *d_in, ofdm_cf32 *d_out, long long n
     if (nframes > 0 && !d_eps) return fail(OFDM_E_ARG, "%s: null d_eps", fn);
     if (!aligned(d_out, 16)) return fail(OFDM_E_ARG, "%s: d_out must be 16-byte aligned", fn);
     if (nframes == 0) return OFDM_OK;
-    const uintptr_t a = reinterpret_cast<uintptr_t>(d_in), b = reinterpret_cast<uintptr_t>(d_out);
     const uintptr_t bytes = (uintptr_t)nframes * S * R * (C + cp_len) * sizeof(ofdm_cf32);
-    if (a != b && a < b + bytes && b < a + bytes)
+    if (d_in != d_out && overlaps(d_in, bytes, d_out, bytes))
         return fail(OFDM_E_ARG, "%s: d_out overlaps d_in (in place, d_out == d_in, or disjoint)", fn);
     return hip_check(ofdm::launch_cfo_derotate(F2(d_in), F2(d_out), nframes, S, R, C, cp_len, d_eps, hs(stream)),
                      "cfo_derotate");
@@ -695,37 +741,21 @@ int ofdm_frame_cfo_derotate(const ofdm_cf32 *d_in, ofdm_cf32 *d_out, long long n
 int ofdm_frame_estimate_cfo(const ofdm_cf32 *d_iq, long long nframes, int S, int R, int C, int prefix,
                             const ofdm_cf32 *d_X, void *d_ws, size_t ws_bytes_, const float *d_eps,
                             ofdm_stream_t stream) {
-    static const char *fn = "ofdm_frame_estimate_cfo";
-    int rc = check_frame_args(d_iq, nframes, S, R, C, prefix, d_ws, fn);
-    if (rc) return rc;
-    if ((rc = check_cfo(fn, nframes, d_eps, C))) return rc;
-    if (!d_X) return fail(OFDM_E_ARG, "%s: null pilots", fn);
-    if (nframes == 0) return OFDM_OK;
-    return estimate_1024(ofdm::iq_f32(F2(d_iq), d_eps), nframes, S, R, prefix, d_X, d_ws, ws_bytes_, stream);
+    return estimate_1024("ofdm_frame_estimate_cfo", cfo_source(d_iq, d_eps), nframes, S, R, C, prefix, d_X, d_ws,
+                         ws_bytes_, stream);
 }
 
 int ofdm_frame_combine_cfo(const ofdm_cf32 *d_iq, long long nframes, int S, int R, int C, int prefix, void *d_ws,
                            size_t ws_bytes_, ofdm_cf32 *d_out, const float *d_eps, ofdm_stream_t stream) {
-    static const char *fn = "ofdm_frame_combine_cfo";
-    if (int st = take_status(fn)) return st;
-    int rc = check_frame_args(d_iq, nframes, S, R, C, prefix, d_out, fn);
-    if (rc) return rc;
-    if ((rc = check_cfo(fn, nframes, d_eps, C))) return rc;
-    if (nframes == 0) return OFDM_OK;
-    return combine_1024(fn, ofdm::iq_f32(F2(d_iq), d_eps), nframes, S, R, prefix, d_ws, ws_bytes_, d_out, stream);
+    return combine_1024("ofdm_frame_combine_cfo", cfo_source(d_iq, d_eps), nframes, S, R, C, prefix, d_ws,
+                        ws_bytes_, d_out, stream);
 }
 
 int ofdm_frame_demod_cfo(const ofdm_cf32 *d_iq, long long nframes, int S, int R, int C, int prefix,
                          const ofdm_cf32 *d_X, void *d_ws, size_t ws_bytes_, ofdm_cf32 *d_out, const float *d_eps,
                          ofdm_stream_t stream) {
-    static const char *fn = "ofdm_frame_demod_cfo";
-    if (int st = take_status(fn)) return st;
-    int rc = check_frame_args(d_iq, nframes, S, R, C, prefix, d_out, fn);
-    if (rc) return rc;
-    if ((rc = check_cfo(fn, nframes, d_eps, C))) return rc;
-    if (!d_X) return fail(OFDM_E_ARG, "%s: null pilots", fn);
-    if (nframes == 0) return OFDM_OK;
-    return demod_1024(ofdm::iq_f32(F2(d_iq), d_eps), nframes, S, R, prefix, d_X, d_ws, ws_bytes_, d_out, stream);
+    return demod_1024("ofdm_frame_demod_cfo", cfo_source(d_iq, d_eps), nframes, S, R, C, prefix, d_X, d_ws,
+                      ws_bytes_, d_out, stream);
 }
 
 // Integer carrier offset (include/ofdm_lsmrc_acquire.h): the refusals in the
@@ -734,9 +764,7 @@ int ofdm_frame_cfo_acquire(const ofdm_cf32 *d_iq, long long nframes, int S, int 
                            const ofdm_cf32 *d_X, int max_shift, float min_ratio, const float *d_eps_in,
                            float *d_eps_out, int *d_shift, float *d_metric, ofdm_stream_t stream) {
     static const char *fn = "ofdm_frame_cfo_acquire";
-    if (nframes < 0) return fail(OFDM_E_ARG, "%s: nframes < 0", fn);
-    if (S < 2) return fail(OFDM_E_ARG, "%s: S=%d, a frame needs a pilot and >= 1 data symbol", fn, S);
-    if (R < 1) return fail(OFDM_E_ARG, "%s: R=%d < 1", fn, R);
+    if (int rc = check_frames(fn, nframes, S, R)) return rc;
     if (cp_len < 0 || cp_len > C) return fail(OFDM_E_ARG, "%s: cp_len=%d out of [0, C]", fn, cp_len);
     if (nframes > 0 && !d_iq) return fail(OFDM_E_ARG, "%s: null d_iq", fn);
     if (nframes > 0 && !d_X) return fail(OFDM_E_ARG, "%s: null d_X", fn);
@@ -744,15 +772,14 @@ int ofdm_frame_cfo_acquire(const ofdm_cf32 *d_iq, long long nframes, int S, int 
     if (!aligned(d_iq, 16)) return fail(OFDM_E_ARG, "%s: d_iq must be 16-byte aligned", fn);
     if (max_shift < 1 || max_shift > OFDM_ACQ_MAX_SHIFT)
         return fail(OFDM_E_ARG, "%s: max_shift=%d out of [1, %d]", fn, max_shift, OFDM_ACQ_MAX_SHIFT);
-    if (!(min_ratio >= 1.f && min_ratio <= 3.402823466e38f))
+    if (!(min_ratio >= 1.f && positive_finite(min_ratio)))
         return fail(OFDM_E_ARG, "%s: min_ratio=%g, the gate needs a finite ratio >= 1", fn, (double)min_ratio);
     if (nframes > 0) {
-        const uintptr_t e0 = reinterpret_cast<uintptr_t>(d_eps_out), e1 = e0 + (uintptr_t)nframes * sizeof(float);
-        const uintptr_t m0 = reinterpret_cast<uintptr_t>(d_metric),
-                        m1 = m0 + (uintptr_t)nframes * (2 * max_shift + 1) * sizeof(float);
-        const uintptr_t s0 = reinterpret_cast<uintptr_t>(d_shift), s1 = s0 + (uintptr_t)nframes * sizeof(int);
-        if (d_metric && e0 < m1 && m0 < e1) return fail(OFDM_E_ARG, "%s: d_eps_out overlaps d_metric", fn);
-        if (d_shift && e0 < s1 && s0 < e1) return fail(OFDM_E_ARG, "%s: d_eps_out overlaps d_shift", fn);
+        const uintptr_t eb = (uintptr_t)nframes * sizeof(float);
+        if (d_metric && overlaps(d_eps_out, eb, d_metric, eb * (2 * max_shift + 1)))
+            return fail(OFDM_E_ARG, "%s: d_eps_out overlaps d_metric", fn);
+        if (d_shift && overlaps(d_eps_out, eb, d_shift, (uintptr_t)nframes * sizeof(int)))
+            return fail(OFDM_E_ARG, "%s: d_eps_out overlaps d_shift", fn);
     }
     if (C < 8 || C > ofdm::FFT_ANY_MAX) return fail(OFDM_E_UNSUPPORTED, "%s: C=%d out of [8, 8192]", fn, C);
     if (4 * max_shift > C)
@@ -770,7 +797,7 @@ int ofdm_frame_estimate_freq(const ofdm_cf32 *d_Y, long long nframes, int S, int
     if (!d_X) return fail(OFDM_E_ARG, "ofdm_frame_estimate_freq: null pilots");
     if (nframes == 0) return OFDM_OK;
     Workspace w;
-    if ((rc = carve(d_ws, ws_bytes_, nframes, S, R, C, !fused_c(C), w))) return rc;
+    if ((rc = carve(d_ws, ws_bytes_, nframes, S, R, C, w))) return rc;
     ws_forget(d_ws);
     rc = hip_check(ofdm::launch_ls_freq(F2(d_Y), (long long)S * R * C, nframes, R, C, F2(d_X), w.Hc,
                                         (long long)R * C, C, 1, w.P, C, 1, hs(stream)),
@@ -784,13 +811,10 @@ int ofdm_frame_combine_freq(const ofdm_cf32 *d_Y, long long nframes, int S, int 
     int rc = check_frame_args(d_Y, nframes, S, R, C, 0, d_out, "ofdm_frame_combine_freq");
     if (rc) return rc;
     if (nframes == 0) return OFDM_OK;
-    WsTag tag;
-    if ((rc = ws_check(d_ws, ws_bytes_, nframes, S, R, C, true, "ofdm_frame_combine_freq", &tag))) return rc;
-    if (tag.lane_order)
-        return fail(OFDM_E_ARG, "ofdm_frame_combine_freq: the workspace holds a time-domain estimate in the "
-                                "fused kernels' lane order (use ofdm_frame_combine)");
     Workspace w;
-    if ((rc = carve(d_ws, ws_bytes_, nframes, S, R, C, !fused_c(C), w))) return rc;
+    if ((rc = open_ws("ofdm_frame_combine_freq", d_ws, ws_bytes_, nframes, S, R, C, true, Layout::Freq,
+                      "time-domain estimate in the fused kernels' lane order (use ofdm_frame_combine)", w)))
+        return rc;
     const long long fst = (long long)S * R * C;
     return hip_check(ofdm::launch_mrc_freq(F2(d_Y) + (long long)R * C, fst, (long long)R * C, nframes,
                                            S - 1, R, C, w.Hc, (long long)R * C, C, 0, w.P, C, 1,
@@ -816,7 +840,7 @@ int ofdm_frame_demod_freq_mfma(const ofdm_cf32 *d_Y, long long nframes, int S, i
     if (!d_X) return fail(OFDM_E_ARG, "ofdm_frame_demod_freq_mfma: null pilots");
     if (nframes == 0) return OFDM_OK;
     Workspace w;
-    if ((rc = carve(d_ws, ws_bytes_, nframes, S, R, C, !fused_c(C), w))) return rc;
+    if ((rc = carve(d_ws, ws_bytes_, nframes, S, R, C, w))) return rc;
     hipStream_t s = hs(stream);
     const long long fst = (long long)S * R * C;
     ws_forget(d_ws);
@@ -838,14 +862,14 @@ int ofdm_frame_ls_partial(const ofdm_cf32 *d_iq, long long nframes, int S, int R
     if (!d_X) return fail(OFDM_E_ARG, "ofdm_frame_ls_partial: null pilots");
     if (nframes == 0) return OFDM_OK;
     Workspace w;
-    if ((rc = carve(d_ws, ws_bytes_, nframes, S, R, C, !fused_c(C), w))) return rc;
+    if ((rc = carve(d_ws, ws_bytes_, nframes, S, R, C, w))) return rc;
     hipStream_t s = hs(stream);
     ws_forget(d_ws);
     if (fused_c(C))
         rc = hip_check(ls_fused(F2(d_iq), nframes, S, R, C, prefix, F2(d_X), w.Hc, w.P, 1, s),
                        "ls_fused");
     else
-        rc = td_staged(F2(d_iq), nframes, S, R, C, prefix, F2(d_X), w, nullptr, 2, s);
+        rc = td_staged(F2(d_iq), nframes, S, R, C, prefix, F2(d_X), w, nullptr, Pass::LsOnly, s);
     if (rc) return rc;
     ws_record(d_ws, ws_bytes_, nframes, S, R, C, lane_c(C), true);
     // bins 1..C-1 of the bin-layout P -> [F][K]
@@ -855,6 +879,10 @@ int ofdm_frame_ls_partial(const ofdm_cf32 *d_iq, long long nframes, int S, int R
                      "copy partial P");
 }
 
+// what the antenna-split combiners find in a workspace of the frequency-domain entries
+static const char *const NOT_TIME_DOMAIN =
+    "frequency-domain estimate, not the time-domain one of ofdm_frame_ls_partial / ofdm_frame_estimate";
+
 int ofdm_frame_mrc_partial(const ofdm_cf32 *d_iq, long long nframes, int S, int R, int C,
                            int prefix, void *d_ws, size_t ws_bytes_, ofdm_cf32 *d_num,
                            ofdm_stream_t stream) {
@@ -862,19 +890,16 @@ int ofdm_frame_mrc_partial(const ofdm_cf32 *d_iq, long long nframes, int S, int 
     int rc = check_frame_args(d_iq, nframes, S, R, C, prefix, d_num, "ofdm_frame_mrc_partial");
     if (rc) return rc;
     if (nframes == 0) return OFDM_OK;
-    WsTag tag;
-    if ((rc = ws_check(d_ws, ws_bytes_, nframes, S, R, C, false, "ofdm_frame_mrc_partial", &tag))) return rc;
-    if (tag.lane_order != lane_c(C))
-        return fail(OFDM_E_ARG, "ofdm_frame_mrc_partial: the workspace holds a frequency-domain estimate, "
-                                "not the time-domain one of ofdm_frame_ls_partial / ofdm_frame_estimate");
     Workspace w;
-    if ((rc = carve(d_ws, ws_bytes_, nframes, S, R, C, !fused_c(C), w))) return rc;
+    if ((rc = open_ws("ofdm_frame_mrc_partial", d_ws, ws_bytes_, nframes, S, R, C, false, Layout::Receiver,
+                      NOT_TIME_DOMAIN, w)))
+        return rc;
     hipStream_t s = hs(stream);
     if (fused_c(C))
-        return hip_check(mrc_fused(F2(d_iq), nframes, S, R, C, prefix, w.Hc, w.P,
-                                                 F2(d_num), 1, s, w.tickets),
+        return hip_check(mrc_fused(F2(d_iq), nframes, S, R, C, prefix, w.Hc, w.P, F2(d_num), Pass::Numerator, s,
+                                   w.tickets),
                          "mrc_fused");
-    return td_staged(F2(d_iq), nframes, S, R, C, prefix, nullptr, w, F2(d_num), 1, s);
+    return td_staged(F2(d_iq), nframes, S, R, C, prefix, nullptr, w, F2(d_num), Pass::Numerator, s);
 }
 
 int ofdm_frame_mrc_partial_range(const ofdm_cf32 *d_iq, long long nframes, long long f0, long long count, int S,
@@ -887,21 +912,17 @@ int ofdm_frame_mrc_partial_range(const ofdm_cf32 *d_iq, long long nframes, long 
     if (count == 0) return OFDM_OK;
     int rc = check_frame_args(d_iq, nframes, S, R, C, prefix, d_num, fn);
     if (rc) return rc;
-    WsTag tag;
-    if ((rc = ws_check(d_ws, ws_bytes_, nframes, S, R, C, false, fn, &tag))) return rc;
-    if (tag.lane_order != lane_c(C))
-        return fail(OFDM_E_ARG, "%s: the workspace holds a frequency-domain estimate, not the time-domain one of "
-                                "ofdm_frame_ls_partial / ofdm_frame_estimate", fn);
     Workspace w;
-    if ((rc = carve(d_ws, ws_bytes_, nframes, S, R, C, !fused_c(C), w))) return rc;
+    if ((rc = open_ws(fn, d_ws, ws_bytes_, nframes, S, R, C, false, Layout::Receiver, NOT_TIME_DOMAIN, w))) return rc;
     hipStream_t s = hs(stream);
     const float2 *iq = F2(d_iq) + f0 * (long long)S * R * (C + prefix);
     Workspace v = w;  // the range's estimate: frames f0 .. in the same [F][R][C] / [F][C] layout
     v.Hc += f0 * (long long)R * C;
     v.P += f0 * C;
     if (fused_c(C))
-        return hip_check(mrc_fused(iq, count, S, R, C, prefix, v.Hc, v.P, F2(d_num), 1, s, w.tickets), fn);
-    return td_staged(iq, count, S, R, C, prefix, nullptr, v, F2(d_num), 1, s);
+        return hip_check(mrc_fused(iq, count, S, R, C, prefix, v.Hc, v.P, F2(d_num), Pass::Numerator, s, w.tickets),
+                         fn);
+    return td_staged(iq, count, S, R, C, prefix, nullptr, v, F2(d_num), Pass::Numerator, s);
 }
 
 int ofdm_symbols_demod(const ofdm_cf32 *d_sym, long long nsym, int R, int C, int prefix, const void *d_ws,
@@ -915,14 +936,9 @@ int ofdm_symbols_demod(const ofdm_cf32 *d_sym, long long nsym, int R, int C, int
         return fail(OFDM_E_UNSUPPORTED, "%s: C=%d (the fused receivers cover C = 1024, 2048, 4096)", fn, C);
     if (prefix < 0 || prefix > C) return fail(OFDM_E_ARG, "%s: prefix=%d out of [0, C]", fn, prefix);
     if (!aligned(d_sym, 16)) return fail(OFDM_E_ARG, "%s: input must be 16-byte aligned", fn);
-    WsTag tag;
-    {
-        std::lock_guard<std::mutex> lock(g_ws_mu);
-        auto it = g_ws.find(d_ws);
-        if (it == g_ws.end())
-            return fail(OFDM_E_ARG, "%s: the workspace holds no estimate (run ofdm_frame_estimate on it first)", fn);
-        tag = it->second;
-    }
+    WsTag tag;  // any batch's estimate serves: its own messages, and no nframes or S to compare
+    if (!ws_lookup(d_ws, tag))
+        return fail(OFDM_E_ARG, "%s: the workspace holds no estimate (run ofdm_frame_estimate on it first)", fn);
     if (tag.R != R || tag.C != C || tag.bytes != ws_bytes_)
         return fail(OFDM_E_ARG, "%s: the workspace estimate is for R=%d C=%d (%zu bytes), called with R=%d C=%d "
                                 "(%zu bytes)", fn, tag.R, tag.C, tag.bytes, R, C, ws_bytes_);
@@ -933,15 +949,14 @@ int ofdm_symbols_demod(const ofdm_cf32 *d_sym, long long nsym, int R, int C, int
         return fail(OFDM_E_ARG, "%s: frame %lld outside the workspace's [0, %lld)", fn, frame, tag.F);
     if (nsym == 0) return OFDM_OK;
     Workspace w;
-    int rc = carve(const_cast<void *>(d_ws), ws_bytes_, tag.F, tag.S, R, C, false, w);
-    if (rc) return rc;
+    if (int rc = carve(d_ws, ws_bytes_, tag.F, tag.S, R, C, w)) return rc;
     // The fused MRC kernels read data symbols 1..S-1 of frame 0 at
     // iq + s * R * (C + prefix) and never touch symbol 0 (the pilot, read by
     // the LS kernels only): a "frame" whose symbol 1 is d_sym[0] is the run.
     const long long row = (long long)R * (C + prefix);
     const float2 *iq = reinterpret_cast<const float2 *>(reinterpret_cast<uintptr_t>(d_sym) - (uintptr_t)(row * 8));
     return hip_check(mrc_fused(iq, 1, (int)(nsym + 1), R, C, prefix, w.Hc + frame * (long long)R * C,
-                               w.P + frame * C, F2(d_out), 0, hs(stream), w.tickets),
+                               w.P + frame * C, F2(d_out), Pass::Combine, hs(stream), w.tickets),
                      fn);
 }
 
@@ -952,10 +967,10 @@ int ofdm_frame_export_estimate(const void *d_ws, size_t ws_bytes_, long long nfr
         return fail(OFDM_E_ARG, "ofdm_frame_export_estimate: frame %lld outside [0, %lld)", frame, nframes);
     if (S < 2 || R < 1 || !valid_c(C)) return fail(OFDM_E_ARG, "ofdm_frame_export_estimate: bad geometry");
     WsTag tag;
-    int rc = ws_check(d_ws, ws_bytes_, nframes, S, R, C, false, "ofdm_frame_export_estimate", &tag);
-    if (rc) return rc;
     Workspace w;
-    if ((rc = carve(const_cast<void *>(d_ws), ws_bytes_, nframes, S, R, C, !fused_c(C), w))) return rc;
+    if (int rc = open_ws("ofdm_frame_export_estimate", d_ws, ws_bytes_, nframes, S, R, C, false, Layout::Any, "", w,
+                         &tag))
+        return rc;
     return hip_check(ofdm::launch_export_estimate(w.Hc + frame * R * C, w.P + frame * C, R, C, tag.lane_order,
                                                   F2(d_Hconj), d_Hsqrd, hs(stream)),
                      "ofdm_frame_export_estimate");
@@ -975,10 +990,8 @@ int ofdm_frame_estimate_denoise(void *d_ws, size_t ws_bytes_, long long nframes,
     // a full estimate of this geometry, of any estimator: the tag says which layout.  No work tickets,
     // no sticky status; the registry entry stays as it is (the denoised estimate serves every consumer).
     WsTag tag;
-    int rc = ws_check(d_ws, ws_bytes_, nframes, S, R, C, true, fn, &tag);
-    if (rc) return rc;
     Workspace w;
-    if ((rc = carve(d_ws, ws_bytes_, nframes, S, R, C, !fused_c(C), w))) return rc;
+    if (int rc = open_ws(fn, d_ws, ws_bytes_, nframes, S, R, C, true, Layout::Any, "", w, &tag)) return rc;
     return hip_check(ofdm::launch_estimate_denoise(w.Hc, w.P, nframes, R, C, tag.lane_order, taps_post, taps_pre,
                                                    hs(stream)),
                      fn);
@@ -989,13 +1002,8 @@ int ofdm_frame_estimate_denoise(void *d_ws, size_t ws_bytes_, long long nframes,
 // bin-indexed in all of them).  Returns 1 for the nframes == 0 no-op.
 static int soft_args(const char *fn, const void *d_z, long long nframes, int S, int R, int C, const void *d_ws,
                      size_t ws_bytes_, int modulation, const void *d_nv, const float **P) {
-    if (modulation != OFDM_MOD_QPSK && modulation != OFDM_MOD_QAM16 && modulation != OFDM_MOD_QAM64 &&
-        modulation != OFDM_MOD_QAM256)
-        return fail(OFDM_E_ARG, "%s: modulation=%d (OFDM_MOD_QPSK 2, _QAM16 4, _QAM64 6 or _QAM256 8)", fn, modulation);
-    if (nframes < 0) return fail(OFDM_E_ARG, "%s: nframes < 0", fn);
-    if (S < 2) return fail(OFDM_E_ARG, "%s: S=%d, a frame needs a pilot and >= 1 data symbol", fn, S);
-    if (R < 1) return fail(OFDM_E_ARG, "%s: R=%d < 1", fn, R);
-    if (!valid_c(C)) return fail(OFDM_E_UNSUPPORTED, "%s: C=%d out of [2, 8192]", fn, C);
+    if (int rc = check_modulation(fn, modulation)) return rc;
+    if (int rc = check_geometry(fn, nframes, S, R, C)) return rc;
     if (nframes == 0) return 1;
     if (!d_z || !d_nv || !d_ws) return fail(OFDM_E_ARG, "%s: null pointer", fn);
     if (!aligned(d_z, 16)) return fail(OFDM_E_ARG, "%s: d_z must be 16-byte aligned", fn);
@@ -1003,10 +1011,8 @@ static int soft_args(const char *fn, const void *d_z, long long nframes, int S, 
     if (!ofdm::soft_demap_supported(nframes, S, C))
         return fail(OFDM_E_UNSUPPORTED, "%s: nframes=%lld S=%d C=%d: a frame's (S-1)*(C-1) elements and the batch's "
                                         "tiles of 1024 must stay below 2^31", fn, nframes, S, C);
-    int rc = ws_check(d_ws, ws_bytes_, nframes, S, R, C, true, fn);
-    if (rc) return rc;
     Workspace w;
-    if ((rc = carve(const_cast<void *>(d_ws), ws_bytes_, nframes, S, R, C, !fused_c(C), w))) return rc;
+    if (int rc = open_ws(fn, d_ws, ws_bytes_, nframes, S, R, C, true, Layout::Any, "", w)) return rc;
     *P = w.P;
     return OFDM_OK;
 }
@@ -1026,7 +1032,7 @@ int ofdm_frame_soft_demap(const ofdm_cf32 *d_z, long long nframes, int S, int R,
     static const char *fn = "ofdm_frame_soft_demap";
     if (llr_format != OFDM_LLR_F32 && llr_format != OFDM_LLR_I8)
         return fail(OFDM_E_ARG, "%s: llr_format=%d (OFDM_LLR_F32 0 or OFDM_LLR_I8 1)", fn, llr_format);
-    if (llr_format == OFDM_LLR_I8 && !(llr_scale > 0.f && llr_scale <= 3.402823466e38f))
+    if (llr_format == OFDM_LLR_I8 && !positive_finite(llr_scale))
         return fail(OFDM_E_ARG, "%s: llr_scale=%g, OFDM_LLR_I8 needs a positive finite scale", fn, (double)llr_scale);
     const float *P = nullptr;
     if (int rc = soft_args(fn, d_z, nframes, S, R, C, d_ws, ws_bytes_, modulation, d_noise_var, &P))
@@ -1038,56 +1044,16 @@ int ofdm_frame_soft_demap(const ofdm_cf32 *d_z, long long nframes, int S, int R,
                      fn);
 }
 
-// Phase tracking: every refusal before any device work; the workspace as the
-// soft output takes it (a full estimate of this geometry: P is bin-indexed in
-// all of them), only read.
-int ofdm_frame_phase_track(const ofdm_cf32 *d_z, long long nframes, int S, int R, int C, const void *d_ws,
-                           size_t ws_bytes_, int modulation, ofdm_cf32 *d_out, float *d_phase, ofdm_stream_t stream) {
-    static const char *fn = "ofdm_frame_phase_track";
-    if (modulation != OFDM_MOD_QPSK && modulation != OFDM_MOD_QAM16 && modulation != OFDM_MOD_QAM64 &&
-        modulation != OFDM_MOD_QAM256)
-        return fail(OFDM_E_ARG, "%s: modulation=%d (OFDM_MOD_QPSK 2, _QAM16 4, _QAM64 6 or _QAM256 8)", fn, modulation);
-    if (nframes < 0) return fail(OFDM_E_ARG, "%s: nframes < 0", fn);
-    if (S < 2) return fail(OFDM_E_ARG, "%s: S=%d, a frame needs a pilot and >= 1 data symbol", fn, S);
-    if (R < 1) return fail(OFDM_E_ARG, "%s: R=%d < 1", fn, R);
-    if (!valid_c(C)) return fail(OFDM_E_UNSUPPORTED, "%s: C=%d out of [2, 8192]", fn, C);
-    if (nframes == 0) return OFDM_OK;
-    if (!d_z) return fail(OFDM_E_ARG, "%s: null d_z", fn);
-    if (!d_out) return fail(OFDM_E_ARG, "%s: null d_out", fn);
-    if (!d_ws) return fail(OFDM_E_ARG, "%s: null d_ws", fn);
-    if (!aligned(d_z, 8)) return fail(OFDM_E_ARG, "%s: d_z must be 8-byte aligned", fn);
-    if (!aligned(d_out, 8)) return fail(OFDM_E_ARG, "%s: d_out must be 8-byte aligned", fn);
-    if (!aligned(d_phase, 4)) return fail(OFDM_E_ARG, "%s: d_phase must be 4-byte aligned", fn);
-    const uintptr_t a = reinterpret_cast<uintptr_t>(d_z), b = reinterpret_cast<uintptr_t>(d_out);
-    const uintptr_t bytes = (uintptr_t)nframes * (S - 1) * (C - 1) * sizeof(ofdm_cf32);
-    if (a != b && a < b + bytes && b < a + bytes)
-        return fail(OFDM_E_ARG, "%s: d_out overlaps d_z (in place, d_out == d_z, or disjoint)", fn);
-    if (d_phase) {
-        const uintptr_t p = reinterpret_cast<uintptr_t>(d_phase), pb = (uintptr_t)nframes * (S - 1) * sizeof(float);
-        if ((p < a + bytes && a < p + pb) || (p < b + bytes && b < p + pb))
-            return fail(OFDM_E_ARG, "%s: d_phase overlaps d_z or d_out", fn);
-    }
-    int rc = ws_check(d_ws, ws_bytes_, nframes, S, R, C, true, fn);
-    if (rc) return rc;
-    Workspace w;
-    if ((rc = carve(const_cast<void *>(d_ws), ws_bytes_, nframes, S, R, C, !fused_c(C), w))) return rc;
-    return hip_check(ofdm::launch_phase_track(F2(d_z), nframes, S, C, w.P, modulation, F2(d_out), d_phase, hs(stream)),
-                     fn);
-}
-
-// Phase and timing tracking (include/ofdm_lsmrc_timing.h): ofdm_frame_phase_track's
-// rules, with one more optional output.
-int ofdm_frame_timing_track(const ofdm_cf32 *d_z, long long nframes, int S, int R, int C, const void *d_ws,
-                            size_t ws_bytes_, int modulation, ofdm_cf32 *d_out, float *d_phase, float *d_timing,
-                            ofdm_stream_t stream) {
-    static const char *fn = "ofdm_frame_timing_track";
-    if (modulation != OFDM_MOD_QPSK && modulation != OFDM_MOD_QAM16 && modulation != OFDM_MOD_QAM64 &&
-        modulation != OFDM_MOD_QAM256)
-        return fail(OFDM_E_ARG, "%s: modulation=%d (OFDM_MOD_QPSK 2, _QAM16 4, _QAM64 6 or _QAM256 8)", fn, modulation);
-    if (nframes < 0) return fail(OFDM_E_ARG, "%s: nframes < 0", fn);
-    if (S < 2) return fail(OFDM_E_ARG, "%s: S=%d, a frame needs a pilot and >= 1 data symbol", fn, S);
-    if (R < 1) return fail(OFDM_E_ARG, "%s: R=%d < 1", fn, R);
-    if (!valid_c(C)) return fail(OFDM_E_UNSUPPORTED, "%s: C=%d out of [2, 8192]", fn, C);
+// Phase tracking, and phase and timing tracking (include/ofdm_lsmrc_timing.h:
+// the same rules with one more optional output, d_timing): every refusal
+// before any device work, in the order the two headers list; the workspace as
+// the soft output takes it (a full estimate of this geometry: P is bin-indexed
+// in all of them), only read.
+static int track(const char *fn, bool timing, const ofdm_cf32 *d_z, long long nframes, int S, int R, int C,
+                 const void *d_ws, size_t ws_bytes_, int modulation, ofdm_cf32 *d_out, float *d_phase, float *d_timing,
+                 ofdm_stream_t stream) {
+    if (int rc = check_modulation(fn, modulation)) return rc;
+    if (int rc = check_geometry(fn, nframes, S, R, C)) return rc;
     if (nframes == 0) return OFDM_OK;
     if (!d_z) return fail(OFDM_E_ARG, "%s: null d_z", fn);
     if (!d_out) return fail(OFDM_E_ARG, "%s: null d_out", fn);
@@ -1096,25 +1062,36 @@ int ofdm_frame_timing_track(const ofdm_cf32 *d_z, long long nframes, int S, int 
     if (!aligned(d_out, 8)) return fail(OFDM_E_ARG, "%s: d_out must be 8-byte aligned", fn);
     if (!aligned(d_phase, 4)) return fail(OFDM_E_ARG, "%s: d_phase must be 4-byte aligned", fn);
     if (!aligned(d_timing, 4)) return fail(OFDM_E_ARG, "%s: d_timing must be 4-byte aligned", fn);
-    const uintptr_t a = reinterpret_cast<uintptr_t>(d_z), b = reinterpret_cast<uintptr_t>(d_out);
-    const uintptr_t bytes = (uintptr_t)nframes * (S - 1) * (C - 1) * sizeof(ofdm_cf32);
-    const uintptr_t pb = (uintptr_t)nframes * (S - 1) * sizeof(float);
-    if (a != b && a < b + bytes && b < a + bytes)
+    const uintptr_t zb = (uintptr_t)nframes * (S - 1) * (C - 1) * sizeof(ofdm_cf32);  // d_z and d_out
+    const uintptr_t pb = (uintptr_t)nframes * (S - 1) * sizeof(float);                // d_phase and d_timing
+    if (d_z != d_out && overlaps(d_z, zb, d_out, zb))
         return fail(OFDM_E_ARG, "%s: d_out overlaps d_z (in place, d_out == d_z, or disjoint)", fn);
-    const uintptr_t p = reinterpret_cast<uintptr_t>(d_phase), t = reinterpret_cast<uintptr_t>(d_timing);
-    if (d_phase && ((p < a + bytes && a < p + pb) || (p < b + bytes && b < p + pb)))
+    if (d_phase && (overlaps(d_phase, pb, d_z, zb) || overlaps(d_phase, pb, d_out, zb)))
         return fail(OFDM_E_ARG, "%s: d_phase overlaps d_z or d_out", fn);
-    if (d_timing && ((t < a + bytes && a < t + pb) || (t < b + bytes && b < t + pb)))
+    if (d_timing && (overlaps(d_timing, pb, d_z, zb) || overlaps(d_timing, pb, d_out, zb)))
         return fail(OFDM_E_ARG, "%s: d_timing overlaps d_z or d_out", fn);
-    if (d_timing && d_phase && t < p + pb && p < t + pb)
+    if (d_timing && d_phase && overlaps(d_timing, pb, d_phase, pb))
         return fail(OFDM_E_ARG, "%s: d_timing overlaps d_phase", fn);
-    int rc = ws_check(d_ws, ws_bytes_, nframes, S, R, C, true, fn);
-    if (rc) return rc;
     Workspace w;
-    if ((rc = carve(const_cast<void *>(d_ws), ws_bytes_, nframes, S, R, C, !fused_c(C), w))) return rc;
-    return hip_check(ofdm::launch_timing_track(F2(d_z), nframes, S, C, w.P, modulation, F2(d_out), d_phase, d_timing,
-                                               hs(stream)),
+    if (int rc = open_ws(fn, d_ws, ws_bytes_, nframes, S, R, C, true, Layout::Any, "", w)) return rc;
+    hipStream_t s = hs(stream);
+    return hip_check(timing ? ofdm::launch_timing_track(F2(d_z), nframes, S, C, w.P, modulation, F2(d_out), d_phase,
+                                                        d_timing, s)
+                            : ofdm::launch_phase_track(F2(d_z), nframes, S, C, w.P, modulation, F2(d_out), d_phase, s),
                      fn);
+}
+
+int ofdm_frame_phase_track(const ofdm_cf32 *d_z, long long nframes, int S, int R, int C, const void *d_ws,
+                           size_t ws_bytes_, int modulation, ofdm_cf32 *d_out, float *d_phase, ofdm_stream_t stream) {
+    return track("ofdm_frame_phase_track", false, d_z, nframes, S, R, C, d_ws, ws_bytes_, modulation, d_out, d_phase,
+                 nullptr, stream);
+}
+
+int ofdm_frame_timing_track(const ofdm_cf32 *d_z, long long nframes, int S, int R, int C, const void *d_ws,
+                            size_t ws_bytes_, int modulation, ofdm_cf32 *d_out, float *d_phase, float *d_timing,
+                            ofdm_stream_t stream) {
+    return track("ofdm_frame_timing_track", true, d_z, nframes, S, R, C, d_ws, ws_bytes_, modulation, d_out, d_phase,
+                 d_timing, stream);
 }
 
 int ofdm_synth_frames(ofdm_cf32 *d_iq, long long nframes, int S, int R, int C, int prefix,

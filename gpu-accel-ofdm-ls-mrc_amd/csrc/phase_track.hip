@@ -13,27 +13,19 @@
 // pilot is phase 0 by construction):
 //   1. phi = theta_(n-1) + (theta_(n-1) - theta_(n-2))   a constant drift costs nothing
 //   2. w_k = z_k e^{-i phi},  d_k = slice(w_k): the nearest point of the 38.211
-//      constellation, per axis t = clamp(floor(x / 2a), -L, L-1), point a (2t+1),
-//      exactly as slice_err of soft_demap.hip
+//      constellation, per axis t = clamp(floor(x / 2a), -L, L-1), point a (2t+1)
+//      (decision.hpp, slice_axis: the slicer of the noise estimate too)
 //   3. g = sum_k P_k w_k conj(d_k) over the elements whose P is positive and finite
 //   4. delta = atan2(Im g, Re g), 0 when g is 0 or not finite;  theta_n = phi + delta
 //   5. out[n][k] = z_k e^{-i theta_n} for every k;  phase[f][n] = theta_n (unwrapped)
 // theta is carried in float64; only its value modulo one turn goes through an
 // f32 sincospi (as cfo.hip does).
 //
-//   k_phase_track<BPS, CH, TPB>  one workgroup of TPB threads per frame: frames
-//       are the parallel dimension, the rows of a frame are a serial chain
-//       load -> rotate/slice/accumulate -> reduce -> atan2 -> rotate -> store,
-//       and its latency, not its bytes, is what can bound the kernel.  Thread t
-//       holds the elements k = c*TPB + t, c < CH, of a row (CH * TPB >= K) in
-//       registers, and the next two rows' in two more sets: a row's loads are
+//   k_phase_track<BPS, CH, TPB>  one workgroup of TPB threads per frame, the
+//       trackers' rows of decision.hpp (thread t holds the elements
+//       k = c*TPB + t, c < CH, of a row and P in registers); a row's loads are
 //       issued two rows ahead and stay in flight while those rows reduce.
-//       P by output position is loaded once per frame into CH registers
-//       (0 where it is not positive and finite).  Rows are only 8-B aligned (K
-//       is odd for every even C): every access is one 8-B element per lane,
-//       512 B contiguous per wave instruction, nontemporal both ways -- no
-//       head/tail case, and in place each thread writes its own elements
-//       only and uses nothing it read from another's.  g: per thread over c in order, then within the wave by
+//       g: per thread over c in order, then within the wave by
 //       DPP butterflies (quad, half-row, row: every lane holds its row's sum)
 //       and the four row sums in lane order; the wave sums meet through one of
 //       two LDS slot sets (row parity), so one barrier per row suffices: a wave
@@ -41,75 +33,16 @@
 //       barrier of row n+1, i.e. has read row n's.  Every thread then adds the
 //       wave sums in wave order: no atomics, the same bits on every run.
 //       <4, 256> serves K <= 1024, <8, 1024> every K up to 8192.
-#include "common.hpp"
+#include "decision.hpp"
 #include "launch.hpp"
 
 namespace ofdm {
 namespace pt {
 
-template <int BPS>
-__device__ __forceinline__ constexpr float qam_a() {
-    return BPS == 2 ? 0.70710678118654752f
-         : BPS == 4 ? 0.31622776601683794f
-         : BPS == 6 ? 0.15430334996209191f
-                    : 0.076696498884737041f;
-}
+using namespace dd;
 
-__device__ __forceinline__ bool pos_finite(float v) { return v > 0.f && v < __builtin_inff(); }
-__device__ __forceinline__ bool is_finite(float v) {
-    return (__builtin_bit_cast(unsigned, v) & 0x7f800000u) != 0x7f800000u;
-}
-
-// the nearest point of one axis: a (2 t + 1), t in [-L, L - 1]
-template <int BPS>
-__device__ __forceinline__ float slice_axis(float x) {
-    constexpr float a = qam_a<BPS>();
-    constexpr float L = (float)(1 << (BPS / 2 - 1));
-    float t = __builtin_floorf(x * (0.5f / a));
-    t = __builtin_fminf(__builtin_fmaxf(t, -L), L - 1.f);
-    return (2.f * t + 1.f) * a;
-}
-
-// e^{-i theta}: theta reduced modulo one turn in float64, the rest in f32
-__device__ __forceinline__ float2 cis_neg(double theta) {
-    const double turns = theta * 0.15915494309189535;  // / 2 pi
-    const float r = (float)(turns - __builtin_rint(turns));
-    float sn, cs;
-    sincospif(2.f * r, &sn, &cs);
-    return float2{cs, -sn};
-}
-
-// v + (v of the lane DPP control CTRL names); every lane active
-template <int CTRL>
-__device__ __forceinline__ float dpp_add(float v) {
-    const int o = __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false);
-    return v + __builtin_bit_cast(float, o);
-}
-// the sum over the wave's 64 lanes, the same bits in every lane
-__device__ __forceinline__ float wave_sum(float v) {
-    v = dpp_add<0xB1>(v);   // quad_perm [1, 0, 3, 2]
-    v = dpp_add<0x4E>(v);   // quad_perm [2, 3, 0, 1]
-    v = dpp_add<0x141>(v);  // row_half_mirror: the other quad of the 8
-    v = dpp_add<0x140>(v);  // row_mirror: the other 8 of the row of 16
-    const int b = __builtin_bit_cast(int, v);
-    const float r0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 0));
-    const float r1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 16));
-    const float r2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 32));
-    const float r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 48));
-    return (r0 + r1) + (r2 + r3);
-}
-
-typedef float f2v __attribute__((ext_vector_type(2)));
-
-// Row n's byte offset in its frame, as a scalar the compiler does not see
-// through: the row's base stays in SGPRs with the element's 32-bit offset
-// beside it, instead of one strength-reduced 64-bit VGPR pointer per element,
-// row set and access (96 registers at 16 elements per thread).
-__device__ __forceinline__ unsigned long long row_bytes(int n, int K) {
-    const unsigned long long b = (unsigned long long)n * (unsigned)K * 8u;
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)b), hi = __builtin_amdgcn_readfirstlane((unsigned)(b >> 32));
-    return ((unsigned long long)hi << 32) | lo;
-}
+// e^{-i theta}
+__device__ __forceinline__ float2 cis_neg(double theta) { return cis_neg_turns(theta * 0.15915494309189535); }  // / 2 pi
 
 // z and out may be the same buffer (in place): no __restrict__ on them
 template <int BPS, int CH, int TPB>
@@ -128,6 +61,7 @@ __global__ void __launch_bounds__(TPB) k_phase_track(const float2 *z, int nrows,
     // element c of this thread: k = c*TPB + tid; past the row's end the load
     // is clamped to the last element (no branch around a load: the waits stay
     // counted) and P = 0 keeps it out of the sum; only the store is guarded
+    // (twin: k_timing_track's setup, see decision.hpp)
     unsigned kc[CH];  // byte offset in the row
     float p[CH];
 #pragma unroll
@@ -138,14 +72,7 @@ __global__ void __launch_bounds__(TPB) k_phase_track(const float2 *z, int nrows,
         p[c] = k < K && pos_finite(v) ? v : 0.f;
     }
     const int last = nrows - 1;
-    auto load_row = [&](float2(&r)[CH], int n) {
-        const char *zn = reinterpret_cast<const char *>(zf) + row_bytes(n < last ? n : last, K);
-#pragma unroll
-        for (int c = 0; c < CH; ++c) {
-            const f2v v = __builtin_nontemporal_load(reinterpret_cast<const f2v *>(zn + kc[c]));
-            r[c] = float2{v.x, v.y};
-        }
-    };
+    auto load = [&](float2(&r)[CH], int n) { load_row(r, zf, n, last, K, kc); };
     double th1 = 0.0, th2 = 0.0;  // theta_(n-1), theta_(n-2)
     auto do_row = [&](const float2(&cur)[CH], int n) {
         const double phi = th1 + (th1 - th2);
@@ -191,46 +118,25 @@ __global__ void __launch_bounds__(TPB) k_phase_track(const float2 *z, int nrows,
     // and are older than row n's stores, so the wait for a row's data (the
     // counter is in issue order) never waits for the row before's stores.
     // Past the frame's end the loads repeat the last row and are not used.
+    // (twin: the same rotation in k_timing_track, see decision.hpp)
     float2 r0[CH], r1[CH], r2[CH];
-    load_row(r0, 0);
+    load(r0, 0);
     __builtin_amdgcn_sched_barrier(0);  // row 0's loads all older than row 1's, as in the loop
-    load_row(r1, 1);
+    load(r1, 1);
     int n = 0;
     // whole triples without an exit inside the loop: a break would merge its
     // path into the loop header and the wait there would fall back to "all
     // but the loads just issued", stores of the row before included
     for (; n + 3 <= nrows; n += 3) {
-        load_row(r2, n + 2);
+        load(r2, n + 2);
         do_row(r0, n);
-        load_row(r0, n + 3);
+        load(r0, n + 3);
         do_row(r1, n + 1);
-        load_row(r1, n + 4);
+        load(r1, n + 4);
         do_row(r2, n + 2);
     }
     if (n < nrows) do_row(r0, n);
     if (n + 1 < nrows) do_row(r1, n + 1);
-}
-
-template <int BPS>
-static hipError_t phase_track_t(const float2 *z, long long nframes, int S, int C, const float *P, float2 *out,
-                                float *phase, hipStream_t s) {
-    const int K = C - 1, nrows = S - 1;
-    const long long per_frame = (long long)nrows * K;
-    for (long long f0 = 0; f0 < nframes; f0 += 0x7fffffffll) {  // one launch but for absurd batches
-        const long long n = nframes - f0 < 0x7fffffffll ? nframes - f0 : 0x7fffffffll;
-        const float2 *zi = z + f0 * per_frame;
-        float2 *oi = out + f0 * per_frame;
-        const float *Pi = P + f0 * C;
-        float *ph = phase ? phase + f0 * nrows : nullptr;
-        if (K <= 4 * 256)
-            hipLaunchKernelGGL((k_phase_track<BPS, 4, 256>), dim3((unsigned)n), dim3(256), 0, s, zi, nrows, K, C, Pi, oi,
-                               ph);
-        else
-            hipLaunchKernelGGL((k_phase_track<BPS, 8, 1024>), dim3((unsigned)n), dim3(1024), 0, s, zi, nrows, K, C, Pi,
-                               oi, ph);
-        if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-    }
-    return hipSuccess;
 }
 
 }  // namespace pt
@@ -239,13 +145,22 @@ hipError_t launch_phase_track(const float2 *z, long long nframes, int S, int C, 
                               float *phase, hipStream_t s) {
     if (nframes <= 0) return hipSuccess;
     if (S < 2 || C < 2 || C > 8 * 1024) return hipErrorInvalidValue;
-    switch (bps) {
-    case 2: return pt::phase_track_t<2>(z, nframes, S, C, P, out, phase, s);
-    case 4: return pt::phase_track_t<4>(z, nframes, S, C, P, out, phase, s);
-    case 6: return pt::phase_track_t<6>(z, nframes, S, C, P, out, phase, s);
-    case 8: return pt::phase_track_t<8>(z, nframes, S, C, P, out, phase, s);
-    default: return hipErrorInvalidValue;
-    }
+    const int K = C - 1, nrows = S - 1;
+    const long long per_frame = (long long)nrows * K;
+    return dd::for_bps(bps, [&](auto b) {
+        constexpr int BPS = decltype(b)::value;
+        return dd::for_frame_chunks(nframes, [&](long long f0, unsigned n) {
+            const float2 *zi = z + f0 * per_frame;
+            float2 *oi = out + f0 * per_frame;
+            const float *Pi = P + f0 * C;
+            float *ph = phase ? phase + f0 * nrows : nullptr;
+            if (K <= 4 * 256)
+                hipLaunchKernelGGL((pt::k_phase_track<BPS, 4, 256>), dim3(n), dim3(256), 0, s, zi, nrows, K, C, Pi, oi, ph);
+            else
+                hipLaunchKernelGGL((pt::k_phase_track<BPS, 8, 1024>), dim3(n), dim3(1024), 0, s, zi, nrows, K, C, Pi, oi,
+                                   ph);
+        });
+    });
 }
 
 }  // namespace ofdm

@@ -10,7 +10,8 @@
 // its post-combining gain is P[f*C + j + 1].
 //
 // Constellations: Gray-mapped, unit average energy, 3GPP TS 38.211 5.1.2-5.1.6
-// (QPSK, 16-, 64-, 256-QAM; BPS = 2, 4, 6, 8 bits per symbol).  Bit 2i comes
+// (QPSK, 16-, 64-, 256-QAM; BPS = 2, 4, 6, 8 bits per symbol; a and the slicer
+// are decision.hpp's, shared with the trackers).  Bit 2i comes
 // from the real axis and bit 2i+1 from the imaginary axis, by the same
 // per-axis function; llr > 0 <=> bit 0 more likely.  With x one axis of Z and
 // a the half-distance between neighbouring points,
@@ -53,20 +54,16 @@
 //       Each thread sums its elements in order into eight accumulators, the
 //       workgroup adds them by a fixed tree in LDS: no atomics, the same bits
 //       on every run.
-#include "common.hpp"
+#include "decision.hpp"
 #include "launch.hpp"
 
 namespace ofdm {
 
-constexpr int SD_TPB = 256, SD_TILE = 1024;
+using dd::pos_finite;
+using dd::qam_a;
+using dd::slice_err;
 
-template <int BPS>
-__device__ __forceinline__ constexpr float qam_a() {
-    return BPS == 2 ? 0.70710678118654752f
-         : BPS == 4 ? 0.31622776601683794f
-         : BPS == 6 ? 0.15430334996209191f
-                    : 0.076696498884737041f;
-}
+constexpr int SD_TPB = 256, SD_TILE = 1024;
 
 // the BPS/2 values lambda_i(x) * s of one axis, s4a = s * 4a
 template <int BPS>
@@ -80,8 +77,6 @@ __device__ __forceinline__ void axis_llr(float x, float s4a, float (&l)[BPS / 2]
         l[i] = s4a * t;
     }
 }
-
-__device__ __forceinline__ bool pos_finite(float v) { return v > 0.f && v < __builtin_inff(); }
 
 // LLRs of one element, bit index fastest
 template <int BPS>
@@ -189,16 +184,6 @@ __global__ void __launch_bounds__(SD_TPB) k_soft_demap(const float2 *__restrict_
     if ((unsigned)tid < rem) ob[16 * full + tid] = reinterpret_cast<const unsigned char *>(T)[16 * full + tid];
 }
 
-// x minus the nearest point of one axis: a (2 t + 1), t in [-L, L - 1]
-template <int BPS>
-__device__ __forceinline__ float slice_err(float x) {
-    constexpr float a = qam_a<BPS>();
-    constexpr float L = (float)(1 << (BPS / 2 - 1));
-    float t = __builtin_floorf(x * (0.5f / a));
-    t = __builtin_fminf(__builtin_fmaxf(t, -L), L - 1.f);
-    return x - (2.f * t + 1.f) * a;
-}
-
 template <int BPS>
 __global__ void __launch_bounds__(SD_TPB) k_noise_estimate(const float2 *__restrict__ z, int K, unsigned per_frame,
                                                            int C, const float *__restrict__ P,
@@ -255,19 +240,6 @@ __global__ void __launch_bounds__(SD_TPB) k_noise_estimate(const float2 *__restr
     if (tid == 0) nv[f] = rc[0] ? rs[0] / (float)rc[0] : 0.f;
 }
 
-template <int BPS>
-static hipError_t soft_demap_t(const float2 *z, long long total, int K, unsigned per_frame, int C, const float *P,
-                        const float *nv, int fmt, float llr_scale, void *out, hipStream_t s) {
-    const unsigned tiles = (unsigned)((total + SD_TILE - 1) / SD_TILE);
-    if (fmt == 0)
-        hipLaunchKernelGGL((k_soft_demap<BPS, 0>), dim3(tiles), dim3(SD_TPB), 0, s, z, total, K, per_frame, C, P, nv,
-                           llr_scale, static_cast<unsigned char *>(out));
-    else
-        hipLaunchKernelGGL((k_soft_demap<BPS, 1>), dim3(tiles), dim3(SD_TPB), 0, s, z, total, K, per_frame, C, P, nv,
-                           llr_scale, static_cast<unsigned char *>(out));
-    return hipGetLastError();
-}
-
 bool soft_demap_supported(long long nframes, int S, int C) {
     const long long per_frame = (long long)(S - 1) * (C - 1);
     if (per_frame < 1 || per_frame > 0x7fffffffll - 2 * SD_TILE) return false;
@@ -282,13 +254,18 @@ hipError_t launch_soft_demap(const float2 *z, long long nframes, int S, int C, c
     const int K = C - 1;
     const unsigned per_frame = (unsigned)(S - 1) * (unsigned)K;
     const long long total = nframes * (long long)per_frame;
-    switch (bps) {
-    case 2: return soft_demap_t<2>(z, total, K, per_frame, C, P, nv, fmt, llr_scale, out, s);
-    case 4: return soft_demap_t<4>(z, total, K, per_frame, C, P, nv, fmt, llr_scale, out, s);
-    case 6: return soft_demap_t<6>(z, total, K, per_frame, C, P, nv, fmt, llr_scale, out, s);
-    case 8: return soft_demap_t<8>(z, total, K, per_frame, C, P, nv, fmt, llr_scale, out, s);
-    default: return hipErrorInvalidValue;
-    }
+    const unsigned tiles = (unsigned)((total + SD_TILE - 1) / SD_TILE);
+    unsigned char *o = static_cast<unsigned char *>(out);
+    return dd::for_bps(bps, [&](auto b) {
+        constexpr int BPS = decltype(b)::value;
+        if (fmt == 0)
+            hipLaunchKernelGGL((k_soft_demap<BPS, 0>), dim3(tiles), dim3(SD_TPB), 0, s, z, total, K, per_frame, C, P, nv,
+                               llr_scale, o);
+        else
+            hipLaunchKernelGGL((k_soft_demap<BPS, 1>), dim3(tiles), dim3(SD_TPB), 0, s, z, total, K, per_frame, C, P, nv,
+                               llr_scale, o);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_noise_estimate(const float2 *z, long long nframes, int S, int C, const float *P, int bps,
@@ -297,15 +274,11 @@ hipError_t launch_noise_estimate(const float2 *z, long long nframes, int S, int 
     if (!soft_demap_supported(nframes, S, C)) return hipErrorInvalidValue;
     const int K = C - 1;
     const unsigned per_frame = (unsigned)(S - 1) * (unsigned)K;
-    const dim3 grid((unsigned)nframes), block(SD_TPB);
-    switch (bps) {
-    case 2: hipLaunchKernelGGL(k_noise_estimate<2>, grid, block, 0, s, z, K, per_frame, C, P, nv); break;
-    case 4: hipLaunchKernelGGL(k_noise_estimate<4>, grid, block, 0, s, z, K, per_frame, C, P, nv); break;
-    case 6: hipLaunchKernelGGL(k_noise_estimate<6>, grid, block, 0, s, z, K, per_frame, C, P, nv); break;
-    case 8: hipLaunchKernelGGL(k_noise_estimate<8>, grid, block, 0, s, z, K, per_frame, C, P, nv); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return dd::for_bps(bps, [&](auto b) {
+        hipLaunchKernelGGL(k_noise_estimate<decltype(b)::value>, dim3((unsigned)nframes), dim3(SD_TPB), 0, s, z, K,
+                           per_frame, C, P, nv);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace ofdm

@@ -2,7 +2,8 @@
 // timing drift of a frame's data symbols, behind ofdm_frame_timing_track
 // (include/ofdm_lsmrc_timing.h states the definition in full; no reference
 // counterpart).  The twin of phase_track.hip: same inputs, same frame-per-
-// workgroup design, one more state variable.
+// workgroup design (decision.hpp holds what the two share), one
+// more state variable.
 //
 // A sampling clock offset moves the FFT window of data symbol n by tau_n
 // samples against the pilot's; subcarrier nu is then turned by
@@ -43,86 +44,13 @@
 //       nu and the half flag are derived from k, not kept.
 //       <4, 256> serves K <= 1024, <8, 1024> every K up to 8192 (!REG:
 //       <16, 512>, whose register budget holds a sincospi per element).
-#include "common.hpp"
+#include "decision.hpp"
 #include "launch.hpp"
 
 namespace ofdm {
 namespace tt {
 
-// the slicer and helpers of phase_track.hip, restated (that file stays as it is)
-template <int BPS>
-__device__ __forceinline__ constexpr float qam_a() {
-    return BPS == 2 ? 0.70710678118654752f
-         : BPS == 4 ? 0.31622776601683794f
-         : BPS == 6 ? 0.15430334996209191f
-                    : 0.076696498884737041f;
-}
-
-__device__ __forceinline__ bool pos_finite(float v) { return v > 0.f && v < __builtin_inff(); }
-__device__ __forceinline__ bool is_finite(float v) {
-    return (__builtin_bit_cast(unsigned, v) & 0x7f800000u) != 0x7f800000u;
-}
-
-template <int BPS>
-__device__ __forceinline__ float slice_axis(float x) {
-    constexpr float a = qam_a<BPS>();
-    constexpr float L = (float)(1 << (BPS / 2 - 1));
-    float t = __builtin_floorf(x * (0.5f / a));
-    t = __builtin_fminf(__builtin_fmaxf(t, -L), L - 1.f);
-    return (2.f * t + 1.f) * a;
-}
-
-// e^{-2 pi i turns}: reduced modulo one turn in float64, the rest in f32
-__device__ __forceinline__ float2 cis_neg_turns(double turns) {
-    const float r = (float)(turns - __builtin_rint(turns));
-    float sn, cs;
-    sincospif(2.f * r, &sn, &cs);
-    return float2{cs, -sn};
-}
-
-template <int CTRL>
-__device__ __forceinline__ float dpp_add(float v) {
-    const int o = __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false);
-    return v + __builtin_bit_cast(float, o);
-}
-// the sum over the wave's 64 lanes, the same bits in every lane
-__device__ __forceinline__ float wave_sum(float v) {
-    v = dpp_add<0xB1>(v);   // quad_perm [1, 0, 3, 2]
-    v = dpp_add<0x4E>(v);   // quad_perm [2, 3, 0, 1]
-    v = dpp_add<0x141>(v);  // row_half_mirror
-    v = dpp_add<0x140>(v);  // row_mirror
-    const int b = __builtin_bit_cast(int, v);
-    const float r0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 0));
-    const float r1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 16));
-    const float r2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 32));
-    const float r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 48));
-    return (r0 + r1) + (r2 + r3);
-}
-
-__device__ __forceinline__ float lane_value(float v, int lane) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), lane));
-}
-// a wave-uniform float64 as a scalar: the recursion's state stays out of the VGPRs
-__device__ __forceinline__ double uniform(double v) {
-    const unsigned long long b = __builtin_bit_cast(unsigned long long, v);
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)b), hi = __builtin_amdgcn_readfirstlane((unsigned)(b >> 32));
-    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
-}
-// the sum over the wave's lanes of a float64, in a fixed order (once per frame)
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-
-typedef float f2v __attribute__((ext_vector_type(2)));
-typedef float f4v __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ unsigned long long row_bytes(int n, int K) {
-    const unsigned long long b = (unsigned long long)n * (unsigned)K * 8u;
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)b), hi = __builtin_amdgcn_readfirstlane((unsigned)(b >> 32));
-    return ((unsigned long long)hi << 32) | lo;
-}
+using namespace dd;
 
 // the signed frequency of output position k (any C)
 __device__ __forceinline__ int signed_bin(int k, int K, int C) {
@@ -146,9 +74,8 @@ __global__ void __launch_bounds__(TPB) k_timing_track(const float2 *z, int nrows
     const float *Pf = P + f * C;
     const int half = C >> 1;  // REG: position k is in the upper half iff k >= C/2
 
-    // element c of this thread: k = c*TPB + tid; past the row's end the load
-    // is clamped to the last element and P = 0 keeps it out of the sums; only
-    // the store is guarded
+    // element c of this thread (twin: k_phase_track's setup, which says why;
+    // see decision.hpp), with the sums for the centroids
     unsigned kc[CH];  // byte offset in the row
     float p[CH];
     double sl = 0.0, snl = 0.0, su = 0.0, snu = 0.0;  // sum P, sum P nu of the two halves
@@ -193,14 +120,7 @@ __global__ void __launch_bounds__(TPB) k_timing_track(const float2 *z, int nrows
     const double invC = uniform(1.0 / (double)C);
 
     const int last = nrows - 1;
-    auto load_row = [&](float2(&r)[CH], int n) {
-        const char *zn = reinterpret_cast<const char *>(zf) + row_bytes(n < last ? n : last, K);
-#pragma unroll
-        for (int c = 0; c < CH; ++c) {
-            const f2v v = __builtin_nontemporal_load(reinterpret_cast<const f2v *>(zn + kc[c]));
-            r[c] = float2{v.x, v.y};
-        }
-    };
+    auto load = [&](float2(&r)[CH], int n) { load_row(r, zf, n, last, K, kc); };
     // e^{-i (theta + 2 pi nu_k tau / C)} for the thread's elements in order of c:
     // fn(c, rotation)
     auto rotations = [&](double theta, double tau, auto &&fn) {
@@ -292,58 +212,24 @@ __global__ void __launch_bounds__(TPB) k_timing_track(const float2 *z, int nrows
             if (timing) timing[f * nrows + n] = (float)ta;
         }
     };
-    // three register sets, rows rotating through them, as in k_phase_track:
-    // row n + 2's loads go out before row n is touched and are older than row
-    // n's stores.  Past the frame's end the loads repeat the last row and are
-    // not used.
+    // three register sets, rows rotating through them (twin: the same
+    // rotation in k_phase_track, which says why it has this shape; see
+    // decision.hpp)
     float2 r0[CH], r1[CH], r2[CH];
-    load_row(r0, 0);
+    load(r0, 0);
     __builtin_amdgcn_sched_barrier(0);
-    load_row(r1, 1);
+    load(r1, 1);
     int n = 0;
     for (; n + 3 <= nrows; n += 3) {
-        load_row(r2, n + 2);
+        load(r2, n + 2);
         do_row(r0, n);
-        load_row(r0, n + 3);
+        load(r0, n + 3);
         do_row(r1, n + 1);
-        load_row(r1, n + 4);
+        load(r1, n + 4);
         do_row(r2, n + 2);
     }
     if (n < nrows) do_row(r0, n);
     if (n + 1 < nrows) do_row(r1, n + 1);
-}
-
-template <int BPS, bool REG>
-static hipError_t timing_track_t(const float2 *z, long long nframes, int S, int C, const float *P, float2 *out,
-                                 float *phase, float *timing, hipStream_t s) {
-    const int K = C - 1, nrows = S - 1;
-    const long long per_frame = (long long)nrows * K;
-    for (long long f0 = 0; f0 < nframes; f0 += 0x7fffffffll) {  // one launch but for absurd batches
-        const long long n = nframes - f0 < 0x7fffffffll ? nframes - f0 : 0x7fffffffll;
-        const float2 *zi = z + f0 * per_frame;
-        float2 *oi = out + f0 * per_frame;
-        const float *Pi = P + f0 * C;
-        float *ph = phase ? phase + f0 * nrows : nullptr;
-        float *tm = timing ? timing + f0 * nrows : nullptr;
-        if (K <= 4 * 256)
-            hipLaunchKernelGGL((k_timing_track<BPS, 4, 256, REG>), dim3((unsigned)n), dim3(256), 0, s, zi, nrows, K, C,
-                               Pi, oi, ph, tm);
-        else if constexpr (REG)
-            hipLaunchKernelGGL((k_timing_track<BPS, 8, 1024, true>), dim3((unsigned)n), dim3(1024), 0, s, zi, nrows, K,
-                               C, Pi, oi, ph, tm);
-        else  // a sincospi per element does not fit 128 registers: half the threads, twice the budget
-            hipLaunchKernelGGL((k_timing_track<BPS, 16, 512, false>), dim3((unsigned)n), dim3(512), 0, s, zi, nrows, K,
-                               C, Pi, oi, ph, tm);
-        if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-    }
-    return hipSuccess;
-}
-
-template <int BPS>
-static hipError_t timing_track_b(const float2 *z, long long nframes, int S, int C, const float *P, float2 *out,
-                                 float *phase, float *timing, hipStream_t s) {
-    return C % 2 == 0 ? timing_track_t<BPS, true>(z, nframes, S, C, P, out, phase, timing, s)
-                      : timing_track_t<BPS, false>(z, nframes, S, C, P, out, phase, timing, s);
 }
 
 }  // namespace tt
@@ -352,13 +238,30 @@ hipError_t launch_timing_track(const float2 *z, long long nframes, int S, int C,
                                float *phase, float *timing, hipStream_t s) {
     if (nframes <= 0) return hipSuccess;
     if (S < 2 || C < 2 || C > 8 * 1024) return hipErrorInvalidValue;
-    switch (bps) {
-    case 2: return tt::timing_track_b<2>(z, nframes, S, C, P, out, phase, timing, s);
-    case 4: return tt::timing_track_b<4>(z, nframes, S, C, P, out, phase, timing, s);
-    case 6: return tt::timing_track_b<6>(z, nframes, S, C, P, out, phase, timing, s);
-    case 8: return tt::timing_track_b<8>(z, nframes, S, C, P, out, phase, timing, s);
-    default: return hipErrorInvalidValue;
-    }
+    const int K = C - 1, nrows = S - 1;
+    const long long per_frame = (long long)nrows * K;
+    return dd::for_bps(bps, [&](auto b) {
+        constexpr int BPS = decltype(b)::value;
+        return dd::for_frame_chunks(nframes, [&](long long f0, unsigned n) {
+            const float2 *zi = z + f0 * per_frame;
+            float2 *oi = out + f0 * per_frame;
+            const float *Pi = P + f0 * C;
+            float *ph = phase ? phase + f0 * nrows : nullptr;
+            float *tm = timing ? timing + f0 * nrows : nullptr;
+            if (K <= 4 * 256 && C % 2 == 0)
+                hipLaunchKernelGGL((tt::k_timing_track<BPS, 4, 256, true>), dim3(n), dim3(256), 0, s, zi, nrows, K, C, Pi,
+                                   oi, ph, tm);
+            else if (K <= 4 * 256)
+                hipLaunchKernelGGL((tt::k_timing_track<BPS, 4, 256, false>), dim3(n), dim3(256), 0, s, zi, nrows, K, C, Pi,
+                                   oi, ph, tm);
+            else if (C % 2 == 0)
+                hipLaunchKernelGGL((tt::k_timing_track<BPS, 8, 1024, true>), dim3(n), dim3(1024), 0, s, zi, nrows, K, C,
+                                   Pi, oi, ph, tm);
+            else  // a sincospi per element does not fit 128 registers: half the threads, twice the budget
+                hipLaunchKernelGGL((tt::k_timing_track<BPS, 16, 512, false>), dim3(n), dim3(512), 0, s, zi, nrows, K, C,
+                                   Pi, oi, ph, tm);
+        });
+    });
 }
 
 }  // namespace ofdm

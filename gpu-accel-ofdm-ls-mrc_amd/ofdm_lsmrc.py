@@ -710,16 +710,23 @@ def frame_phase_track(z, ws, F, S, R, C, modulation, out=None, phase=None, strea
     from the estimate in ws (any full estimate of this F, S, R, C).  phase
     (F, S-1) float32, when given, receives the tracked phase of every data
     symbol in radians, unwrapped (include/ofdm_lsmrc.h, "phase tracking")."""
+    return _track("ofdm_frame_phase_track", z, ws, F, S, R, C, modulation, out, stream, phase=phase)
+
+
+def _track(entry, z, ws, F, S, R, C, modulation, out, stream, **per_symbol):
+    """frame_phase_track and frame_timing_track: the entry's optional (F, S-1)
+    float32 outputs by name, in the entry's order."""
     import torch
     if out is None:
         out = c64((F, S - 1, C - 1), z.device)
-    if phase is not None and (not isinstance(phase, torch.Tensor) or phase.dtype != torch.float32
-                              or tuple(phase.shape) != (F, S - 1)):
-        raise OfdmError(f"phase must be a torch.float32 tensor of shape ({F}, {S - 1})")
-    _check(lib().ofdm_frame_phase_track(_dptr(z, "z") if F else None, F, S, R, C, _dptr(ws, "ws") if F else None,
-                                        ws.numel() if F else 0, modulation, _dptr(out, "out") if F else None,
-                                        _dptr(phase, "phase") if F and phase is not None else None, _stream(stream)),
-           "ofdm_frame_phase_track")
+    for name, t in per_symbol.items():
+        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.float32
+                              or tuple(t.shape) != (F, S - 1)):
+            raise OfdmError(f"{name} must be a torch.float32 tensor of shape ({F}, {S - 1})")
+    outs = [_dptr(t, name) if F and t is not None else None for name, t in per_symbol.items()]
+    _check(getattr(lib(), entry)(_dptr(z, "z") if F else None, F, S, R, C, _dptr(ws, "ws") if F else None,
+                                 ws.numel() if F else 0, modulation, _dptr(out, "out") if F else None, *outs,
+                                 _stream(stream)), entry)
     return out
 
 
@@ -746,20 +753,7 @@ def frame_timing_track(z, ws, F, S, R, C, modulation, out=None, phase=None, timi
     frame_phase_track.  phase and timing (F, S-1) float32, when given, receive
     every data symbol's tracked phase (radians, unwrapped) and window offset
     against the pilot's (samples) (include/ofdm_lsmrc_timing.h)."""
-    import torch
-    if out is None:
-        out = c64((F, S - 1, C - 1), z.device)
-    for name, t in (("phase", phase), ("timing", timing)):
-        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.float32
-                              or tuple(t.shape) != (F, S - 1)):
-            raise OfdmError(f"{name} must be a torch.float32 tensor of shape ({F}, {S - 1})")
-    _check(lib().ofdm_frame_timing_track(_dptr(z, "z") if F else None, F, S, R, C, _dptr(ws, "ws") if F else None,
-                                         ws.numel() if F else 0, modulation, _dptr(out, "out") if F else None,
-                                         _dptr(phase, "phase") if F and phase is not None else None,
-                                         _dptr(timing, "timing") if F and timing is not None else None,
-                                         _stream(stream)),
-           "ofdm_frame_timing_track")
-    return out
+    return _track("ofdm_frame_timing_track", z, ws, F, S, R, C, modulation, out, stream, phase=phase, timing=timing)
 
 
 def sampling_offset(timing, C, prefix):
