@@ -13,6 +13,7 @@
 
 #include "../../include/ofdm_lsmrc.h"
 #include "../../include/ofdm_lsmrc_acquire.h"
+#include "../../include/ofdm_lsmrc_decode.h"
 #include "../../include/ofdm_lsmrc_timing.h"
 #include "launch.hpp"
 
@@ -1092,6 +1093,94 @@ int ofdm_frame_timing_track(const ofdm_cf32 *d_z, long long nframes, int S, int 
                             ofdm_stream_t stream) {
     return track("ofdm_frame_timing_track", true, d_z, nframes, S, R, C, d_ws, ws_bytes_, modulation, d_out, d_phase,
                  d_timing, stream);
+}
+
+// Viterbi decoder (include/ofdm_lsmrc_decode.h).  What all three entries
+// check of the code, L and ncw, in the header's order; *T and *n_rx on success.
+static int conv_args(const char *fn, const ofdm_conv_code *code, int L, long long ncw, int *T, long long *n_rx) {
+    if (!code) return fail(OFDM_E_ARG, "%s: null code", fn);
+    if (code->n_out != 2 && code->n_out != 3) return fail(OFDM_E_ARG, "%s: n_out=%d (2 or 3)", fn, code->n_out);
+    for (int i = 0; i < code->n_out; ++i)
+        if (code->g[i] < 1 || code->g[i] > 127)
+            return fail(OFDM_E_ARG, "%s: generator g[%d]=%d outside 1..127", fn, i, code->g[i]);
+    const int p = code->punct_period, n = code->n_out;
+    if (p < 0 || (long long)p * n > 32)
+        return fail(OFDM_E_ARG, "%s: punct_period=%d (0, or 1 <= p with p * n_out <= 32)", fn, p);
+    const unsigned valid = p * n >= 32 ? ~0u : (1u << (p * n)) - 1u;
+    if (code->punct_mask & ~valid)
+        return fail(OFDM_E_ARG, "%s: punct_mask=0x%x has bits at or above p * n_out = %d", fn, code->punct_mask, p * n);
+    if (p > 0 && !code->punct_mask) return fail(OFDM_E_ARG, "%s: punct_mask sends no bit", fn);
+    if (L < 1) return fail(OFDM_E_ARG, "%s: L=%d", fn, L);
+    if (ncw < 0) return fail(OFDM_E_ARG, "%s: ncw=%lld", fn, ncw);
+    if (L > 65530) return fail(OFDM_E_UNSUPPORTED, "%s: L=%d above 65530", fn, L);
+    *T = code->terminated ? L + 6 : L;
+    if (p == 0) {
+        *n_rx = (long long)*T * n;
+    } else {
+        const int w = __builtin_popcount(code->punct_mask), full = *T / p, rest = *T % p;
+        *n_rx = (long long)full * w + __builtin_popcount(code->punct_mask & ((1u << (rest * n)) - 1u));
+    }
+    return OFDM_OK;
+}
+
+int ofdm_conv_coded_len(const ofdm_conv_code *code, int L, long long *n_rx) {
+    static const char *fn = "ofdm_conv_coded_len";
+    int T = 0;
+    long long n = 0;
+    if (int rc = conv_args(fn, code, L, 0, &T, &n)) return rc;
+    if (!n_rx) return fail(OFDM_E_ARG, "%s: null n_rx", fn);
+    *n_rx = n;
+    return OFDM_OK;
+}
+
+int ofdm_viterbi_workspace_bytes(const ofdm_conv_code *code, int L, long long ncw, size_t *bytes) {
+    static const char *fn = "ofdm_viterbi_workspace_bytes";
+    int T = 0;
+    long long n = 0;
+    if (int rc = conv_args(fn, code, L, ncw, &T, &n)) return rc;
+    if (!bytes) return fail(OFDM_E_ARG, "%s: null bytes", fn);
+    *bytes = ofdm::viterbi_scratch_bytes(T, ncw);
+    return OFDM_OK;
+}
+
+int ofdm_viterbi_decode(const void *d_llr, int llr_format, float llr_scale, long long cw_stride, long long ncw, int L,
+                        const ofdm_conv_code *code, unsigned char *d_bits, long long out_stride, int *d_metric,
+                        void *d_scratch, size_t scratch_bytes, ofdm_stream_t stream) {
+    static const char *fn = "ofdm_viterbi_decode";
+    int T = 0;
+    long long n_rx = 0;
+    if (int rc = conv_args(fn, code, L, ncw, &T, &n_rx)) return rc;
+    if (llr_format != OFDM_LLR_F32 && llr_format != OFDM_LLR_I8)
+        return fail(OFDM_E_ARG, "%s: llr_format=%d (OFDM_LLR_F32 0 or OFDM_LLR_I8 1)", fn, llr_format);
+    if (llr_format == OFDM_LLR_F32 && !positive_finite(llr_scale))
+        return fail(OFDM_E_ARG, "%s: llr_scale=%g, OFDM_LLR_F32 needs a positive finite scale", fn, (double)llr_scale);
+    const long long nbytes = (L + 7) / 8;
+    if (cw_stride < n_rx) return fail(OFDM_E_ARG, "%s: cw_stride=%lld below n_rx=%lld", fn, cw_stride, n_rx);
+    if (out_stride < nbytes) return fail(OFDM_E_ARG, "%s: out_stride=%lld below ceil(L/8)=%lld", fn, out_stride, nbytes);
+    if (ncw == 0) return OFDM_OK;
+    if (!d_llr) return fail(OFDM_E_ARG, "%s: null d_llr", fn);
+    if (!d_bits) return fail(OFDM_E_ARG, "%s: null d_bits", fn);
+    const size_t need = ofdm::viterbi_scratch_bytes(T, ncw);
+    if (scratch_bytes < need)
+        return fail(OFDM_E_ARG, "%s: scratch_bytes=%zu below ofdm_viterbi_workspace_bytes=%zu", fn, scratch_bytes, need);
+    if (need && !d_scratch) return fail(OFDM_E_ARG, "%s: null d_scratch", fn);
+    const size_t esz = llr_format == OFDM_LLR_F32 ? 4 : 1;
+    if (!aligned(d_llr, esz)) return fail(OFDM_E_ARG, "%s: d_llr must be 4-byte aligned for OFDM_LLR_F32", fn);
+    if (!aligned(d_metric, 4)) return fail(OFDM_E_ARG, "%s: d_metric must be 4-byte aligned", fn);
+    if (need && !aligned(d_scratch, 8)) return fail(OFDM_E_ARG, "%s: d_scratch must be 8-byte aligned", fn);
+    const uintptr_t lb = (uintptr_t)((ncw - 1) * cw_stride + n_rx) * esz;    // the LLR range, gaps included
+    const uintptr_t bb = (uintptr_t)((ncw - 1) * out_stride + nbytes);       // d_bits likewise
+    const uintptr_t mb = d_metric ? (uintptr_t)ncw * sizeof(int) : 0, sb = d_scratch ? need : 0;
+    if (overlaps(d_bits, bb, d_llr, lb)) return fail(OFDM_E_ARG, "%s: d_bits overlaps d_llr", fn);
+    if (mb && (overlaps(d_metric, mb, d_llr, lb) || overlaps(d_metric, mb, d_bits, bb)))
+        return fail(OFDM_E_ARG, "%s: d_metric overlaps d_llr or d_bits", fn);
+    if (sb && (overlaps(d_scratch, sb, d_llr, lb) || overlaps(d_scratch, sb, d_bits, bb) ||
+               (mb && overlaps(d_scratch, sb, d_metric, mb))))
+        return fail(OFDM_E_ARG, "%s: d_scratch overlaps d_llr, d_bits or d_metric", fn);
+    return hip_check(ofdm::launch_viterbi(d_llr, llr_format, llr_scale, cw_stride, ncw, L, T, n_rx, code->n_out, code->g,
+                                          code->terminated, code->punct_period, code->punct_mask, d_bits, out_stride,
+                                          d_metric, d_scratch, hs(stream)),
+                     fn);
 }
 
 int ofdm_synth_frames(ofdm_cf32 *d_iq, long long nframes, int S, int R, int C, int prefix,

@@ -243,6 +243,20 @@ hipError_t launch_phase_track(const float2 *z, long long nframes, int S, int C, 
 hipError_t launch_timing_track(const float2 *z, long long nframes, int S, int C, const float *P, int bps, float2 *out,
                                float *phase, float *timing, hipStream_t s);
 
+// Viterbi decoder for K = 7 convolutional codes (viterbi.hip states the
+// kernel, include/ofdm_lsmrc_decode.h the definition).  llr: fmt 0 floats, 1
+// signed bytes, codeword c at element c*cw_stride, n_rx elements; T steps of
+// n_out coded bits, generators g, puncturing (p, mask) as ofdm_conv_code's;
+// bits: ceil(L/8) bytes at c*out_stride; metric [ncw] (may be null); scratch:
+// viterbi_scratch_bytes(T, ncw) bytes, 8-B aligned (null where that is 0).
+constexpr int VIT_LDS_STEPS = 4096;      // decisions of up to this many steps stay in LDS (8 B per step)
+constexpr int VIT_ROUND_LDS = 65536;     // workgroups of a launch, each taking codewords in turn: decisions in LDS ...
+constexpr int VIT_ROUND_SCRATCH = 1024;  // ... and in scratch (one 8*T-byte slot each)
+size_t viterbi_scratch_bytes(int T, long long ncw);
+hipError_t launch_viterbi(const void *llr, int fmt, float llr_scale, long long cw_stride, long long ncw, int L, int T,
+                          long long n_rx, int n_out, const int *g, int terminated, int p, unsigned mask,
+                          unsigned char *bits, long long out_stride, int *metric, void *scratch, hipStream_t s);
+
 // OFDM modulator (tx_mod.hip; any C but 1024: fft_any.hip k_tx_any): row i =
 // X + i*ldx (K values, through the bin placement `map`) -> backward FFT ->
 // iq + i*(C+cp): the last cp samples, then the C samples, times 1/peak

@@ -26,6 +26,7 @@ LIB_PATH = os.path.join(HERE, "lib", f"libofdm_lsmrc_{_LIBSEL}.so" if _LIBSEL el
 HEADER_PATH = os.path.join(os.path.dirname(HERE), "include", "ofdm_lsmrc.h")
 ACQUIRE_HEADER_PATH = os.path.join(os.path.dirname(HERE), "include", "ofdm_lsmrc_acquire.h")
 TIMING_HEADER_PATH = os.path.join(os.path.dirname(HERE), "include", "ofdm_lsmrc_timing.h")
+DECODE_HEADER_PATH = os.path.join(os.path.dirname(HERE), "include", "ofdm_lsmrc_decode.h")
 
 _c = ctypes
 _P = _c.c_void_p
@@ -121,9 +122,17 @@ _SIGS_TIMING = {
     "ofdm_pipeline_set_timing_track": (_I, [_P, _I]),
 }
 
+# include/ofdm_lsmrc_decode.h (likewise)
+_SIGS_DECODE = {
+    "ofdm_conv_coded_len": (_I, [_P, _I, _c.POINTER(_LL)]),
+    "ofdm_viterbi_workspace_bytes": (_I, [_P, _I, _LL, _c.POINTER(_c.c_size_t)]),
+    "ofdm_viterbi_decode": (_I, [_P, _I, _c.c_float, _LL, _LL, _I, _P, _P, _LL, _P, _P, _c.c_size_t, _P]),
+}
+
 
 def _all_sigs():
-    return list(_SIGS.items()) + list(_SIGS_ACQUIRE.items()) + list(_SIGS_TIMING.items())
+    return (list(_SIGS.items()) + list(_SIGS_ACQUIRE.items()) + list(_SIGS_TIMING.items())
+            + list(_SIGS_DECODE.items()))
 
 _lib = None
 
@@ -131,14 +140,16 @@ _lib = None
 def build_id():
     """Identity of the product library's build: the first 16 hex digits of
     a SHA-256 over its sources (csrc/, the Makefile, include/ofdm_lsmrc.h,
-    include/ofdm_lsmrc_acquire.h, include/ofdm_lsmrc_timing.h), in sorted order.  PMC profiles record it
+    include/ofdm_lsmrc_acquire.h, include/ofdm_lsmrc_timing.h,
+    include/ofdm_lsmrc_decode.h), in sorted order.  PMC profiles record it
     (scripts/pmc_summary.py) and bench.py attaches a profile's traffic only to
     the build it measured."""
     import hashlib
     h = hashlib.sha256()
     csrc = os.path.join(HERE, "csrc")
     files = [os.path.join(csrc, f) for f in sorted(os.listdir(csrc))] + [os.path.join(HERE, "Makefile"), HEADER_PATH,
-                                                                         ACQUIRE_HEADER_PATH, TIMING_HEADER_PATH]
+                                                                         ACQUIRE_HEADER_PATH, TIMING_HEADER_PATH,
+                                                                         DECODE_HEADER_PATH]
     for f in files:
         if os.path.isfile(f):
             h.update(os.path.basename(f).encode() + b"\0")
@@ -769,6 +780,93 @@ def sampling_offset(timing, C, prefix):
     import torch
     n = torch.arange(1, timing.shape[-1] + 1, dtype=torch.float64, device=timing.device)
     return (timing.to(torch.float64) * n).sum(-1) / (n * n).sum() / (C + prefix)
+
+
+class ConvCode(_c.Structure):
+    """ofdm_conv_code (include/ofdm_lsmrc_decode.h): a constraint-length-7
+    convolutional code, its termination and its puncturing."""
+    _fields_ = [("n_out", _I), ("g", _I * 3), ("terminated", _I), ("punct_period", _I), ("punct_mask", _c.c_uint)]
+
+    def __init__(self, n_out, g, terminated=True, punct_period=0, punct_mask=0):
+        g = list(g) + [0] * (3 - len(g))
+        super().__init__(n_out, (_I * 3)(*g), int(bool(terminated)), punct_period, punct_mask)
+
+    @classmethod
+    def k7_rate_half(cls, terminated=True):
+        """0133 / 0171 (octal): the 802.11 / DVB / CCSDS code."""
+        return cls(2, (0o133, 0o171), terminated)
+
+    @classmethod
+    def k7_rate_third(cls, terminated=True):
+        return cls(3, (0o133, 0o171, 0o165), terminated)
+
+    @classmethod
+    def wifi_2_3(cls, terminated=True):
+        """802.11 rate 2/3: of every two steps' four coded bits the last is not sent."""
+        return cls(2, (0o133, 0o171), terminated, 2, 0x7)
+
+    @classmethod
+    def wifi_3_4(cls, terminated=True):
+        """802.11 rate 3/4: of every three steps' six coded bits, bits 3 and 4 are not sent."""
+        return cls(2, (0o133, 0o171), terminated, 3, 0x27)
+
+
+def conv_coded_len(code, L):
+    """n_rx: the LLRs a codeword of L information bits has (host arithmetic)."""
+    n = _LL(0)
+    _check(lib().ofdm_conv_coded_len(_c.byref(code), L, _c.byref(n)), "ofdm_conv_coded_len")
+    return n.value
+
+
+def viterbi_workspace_bytes(code, L, ncw):
+    n = _c.c_size_t(0)
+    _check(lib().ofdm_viterbi_workspace_bytes(_c.byref(code), L, ncw, _c.byref(n)), "ofdm_viterbi_workspace_bytes")
+    return n.value
+
+
+def viterbi_decode(llr, code, L, ncw=None, stride=None, scale=1.0, out=None, out_stride=None, metric=None, ws=None,
+                   stream=None):
+    """Viterbi decoding of ncw codewords of L information bits each
+    (include/ofdm_lsmrc_decode.h) -> (bits uint8 [ncw, out_stride], packed,
+    bit t of a codeword in bit t & 7 of byte t >> 3; metric int32 [ncw]).
+    llr: a device tensor, int8 (OFDM_LLR_I8) or float32 (OFDM_LLR_F32,
+    quantised with `scale`); 2-D (ncw, stride), or flat with ncw and stride
+    (default: n_rx) given: codeword c begins at element c * stride.  ws: a byte
+    tensor of viterbi_workspace_bytes (made here if absent and needed)."""
+    import torch
+    if not isinstance(llr, torch.Tensor) or llr.dtype not in (torch.int8, torch.float32):
+        raise OfdmError("llr must be a torch.int8 or torch.float32 device tensor")
+    n_rx = conv_coded_len(code, L)
+    if llr.dim() == 2 and ncw is None and stride is None:
+        ncw, stride = llr.shape
+    if stride is None:
+        stride = n_rx
+    if ncw is None:
+        ncw = 0 if llr.numel() < n_rx else (llr.numel() - n_rx) // stride + 1
+    if ncw > 0 and llr.numel() < (ncw - 1) * stride + n_rx:
+        raise OfdmError(f"llr holds {llr.numel()} elements, {ncw} codewords at stride {stride} need "
+                        f"{(ncw - 1) * stride + n_rx}")
+    nbytes = (L + 7) // 8
+    if out_stride is None:
+        out_stride = out.shape[-1] if out is not None and out.dim() == 2 else nbytes
+    if out is None:
+        out = torch.empty((ncw, out_stride), dtype=torch.uint8, device=llr.device)
+    elif out.dtype != torch.uint8 or (ncw > 0 and out.numel() < (ncw - 1) * out_stride + min(nbytes, out_stride)):
+        raise OfdmError(f"out must be a torch.uint8 tensor of {ncw} rows of {out_stride} bytes")
+    if metric is None:
+        metric = torch.empty(ncw, dtype=torch.int32, device=llr.device)
+    elif metric.dtype != torch.int32 or metric.numel() < ncw:
+        raise OfdmError(f"metric must be a torch.int32 tensor of {ncw} elements")
+    need = viterbi_workspace_bytes(code, L, ncw)
+    if ws is None and need:
+        ws = torch.empty(need, dtype=torch.uint8, device=llr.device)
+    live = ncw > 0
+    _check(lib().ofdm_viterbi_decode(_dptr(llr, "llr") if live else None, 1 if llr.dtype == torch.int8 else 0, scale,
+                                     stride, ncw, L, _c.byref(code), _dptr(out, "out") if live else None, out_stride,
+                                     _dptr(metric, "metric") if live else None,
+                                     _dptr(ws, "ws") if ws is not None and ws.numel() else None,
+                                     ws.numel() if ws is not None else 0, _stream(stream)), "ofdm_viterbi_decode")
+    return out, metric
 
 
 def synth_frames(F, S, R, C, X, prefix=0, seed=1234, frame0=0, noise_std=0.01,
