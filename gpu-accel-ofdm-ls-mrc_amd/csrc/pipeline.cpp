@@ -71,6 +71,8 @@ int herr(hipError_t e, const char *fn, const char *what) {
     return ofdm::set_error(OFDM_E_HIP, buf);
 }
 
+bool positive_finite(float x) { return x > 0.f && x <= 3.402823466e38f; }
+
 #define PL_TRY(expr, fn, what)                           \
     do {                                                 \
         int rc_ = herr((expr), fn, what);                \
@@ -122,7 +124,7 @@ int create(const char *fn, int S, int R, int C, int cp_len, bool sc16, float sca
     *out = nullptr;
     if (chunk_frames < 1 || depth < 1 || depth > 64)
         return err(OFDM_E_ARG, fn, "chunk_frames >= 1 and 1 <= depth <= 64 required");
-    if (sc16 && !(scale > 0.f && scale <= 3.402823466e38f))
+    if (sc16 && !positive_finite(scale))
         return err(OFDM_E_ARG, fn, "sc16 samples need a positive finite scale");
     const size_t ws = ofdm_frame_workspace_bytes(chunk_frames, S, R, C);
     if (ws == 0) return err(OFDM_E_UNSUPPORTED, fn, "bad frame geometry (S >= 2, R >= 1, 2 <= C <= 8192)");
@@ -165,12 +167,17 @@ int create(const char *fn, int S, int R, int C, int cp_len, bool sc16, float sca
     return OFDM_OK;
 }
 
-// the acquire of either format (fmt_sc16: the caller's)
+// an entry of one sample format (fmt_sc16: the caller's) on a pipeline of the other
+int check_format(const char *fn, const ofdm_pipeline *p, bool fmt_sc16) {
+    if (p->sc16 == fmt_sc16) return OFDM_OK;
+    return err(OFDM_E_ARG, fn, p->sc16 ? "the pipeline holds sc16 samples (use the _sc16 entry)"
+                                       : "the pipeline holds fp32 samples (use the entry without _sc16)");
+}
+
+// the acquire of either format
 int acquire(const char *fn, ofdm_pipeline *p, bool fmt_sc16, void **d_iq, ofdm_stream_t *copy_stream) {
     if (!p || !d_iq) return err(OFDM_E_ARG, fn, "null pointer");
-    if (p->sc16 != fmt_sc16)
-        return err(OFDM_E_ARG, fn, p->sc16 ? "the pipeline holds sc16 samples (use the _sc16 entry)"
-                                           : "the pipeline holds fp32 samples (use the entry without _sc16)");
+    if (int rc = check_format(fn, p, fmt_sc16)) return rc;
     auto &s = p->slots[p->next];
     if (s.acquired) return err(OFDM_E_ARG, fn, "slot already acquired: submit it first");
     DeviceGuard dg(p->device);
@@ -188,9 +195,7 @@ int demod_all(const char *fn, ofdm_pipeline *p, bool fmt_sc16, const void *iq, s
               ofdm_cf32 *out) {
     if (!p) return err(OFDM_E_ARG, fn, "null pipeline");
     if (nframes < 0 || (nframes > 0 && (!iq || !out))) return err(OFDM_E_ARG, fn, "bad arguments");
-    if (p->sc16 != fmt_sc16)
-        return err(OFDM_E_ARG, fn, p->sc16 ? "the pipeline holds sc16 samples (use the _sc16 entry)"
-                                           : "the pipeline holds fp32 samples (use the entry without _sc16)");
+    if (int rc = check_format(fn, p, fmt_sc16)) return rc;
     for (long long f0 = 0; f0 < nframes; f0 += p->chunk) {
         const long long n = nframes - f0 < p->chunk ? nframes - f0 : p->chunk;
         void *d = nullptr;
@@ -202,6 +207,90 @@ int demod_all(const char *fn, ofdm_pipeline *p, bool fmt_sc16, const void *iq, s
                fn, "copy-in");
         if ((rc = ofdm_pipeline_submit(p, n, out + (size_t)f0 * p->frame_out))) return rc;
     }
+    return OFDM_OK;
+}
+
+// A chunk's sample source: which family of the public frame entries takes it.
+// Plain: fp32 frames, every C.  Sc16: the slot's int16 frames; Cfo: fp32 frames
+// and the slot's offsets; both have a receiver at C = 1024 only.  A new source
+// is one more kind here and one more line in each of the three functions.
+enum class Source { Plain, Sc16, Cfo };
+using Slot = ofdm_pipeline::Slot;
+const ofdm_sc16 *sc16_of(const Slot &s) { return static_cast<const ofdm_sc16 *>(s.iq); }
+
+int estimate(Source src, const ofdm_pipeline &p, const Slot &s, const ofdm_cf32 *iq, long long n) {
+    if (src == Source::Sc16)
+        return ofdm_frame_estimate_sc16(sc16_of(s), n, p.S, p.R, p.C, p.cp, p.scale, p.X, s.ws, p.ws_bytes, p.s_comp);
+    if (src == Source::Cfo)
+        return ofdm_frame_estimate_cfo(iq, n, p.S, p.R, p.C, p.cp, p.X, s.ws, p.ws_bytes, s.eps, p.s_comp);
+    return ofdm_frame_estimate(iq, n, p.S, p.R, p.C, p.cp, p.X, s.ws, p.ws_bytes, p.s_comp);
+}
+int combine(Source src, const ofdm_pipeline &p, const Slot &s, const ofdm_cf32 *iq, long long n) {
+    if (src == Source::Sc16)
+        return ofdm_frame_combine_sc16(sc16_of(s), n, p.S, p.R, p.C, p.cp, p.scale, s.ws, p.ws_bytes, s.out, p.s_comp);
+    if (src == Source::Cfo)
+        return ofdm_frame_combine_cfo(iq, n, p.S, p.R, p.C, p.cp, s.ws, p.ws_bytes, s.out, s.eps, p.s_comp);
+    return ofdm_frame_combine(iq, n, p.S, p.R, p.C, p.cp, s.ws, p.ws_bytes, s.out, p.s_comp);
+}
+int demod(Source src, const ofdm_pipeline &p, const Slot &s, const ofdm_cf32 *iq, long long n) {
+    if (src == Source::Sc16)
+        return ofdm_frame_demod_sc16(sc16_of(s), n, p.S, p.R, p.C, p.cp, p.scale, p.X, s.ws, p.ws_bytes, s.out, p.s_comp);
+    if (src == Source::Cfo)
+        return ofdm_frame_demod_cfo(iq, n, p.S, p.R, p.C, p.cp, p.X, s.ws, p.ws_bytes, s.out, s.eps, p.s_comp);
+    return ofdm_frame_demod(iq, n, p.S, p.R, p.C, p.cp, p.X, s.ws, p.ws_bytes, s.out, p.s_comp);
+}
+
+// The receiver of one chunk on the compute stream, a single chain: each step
+// is written once and a new one goes in at its place in the order.
+int receive(ofdm_pipeline *p, Slot &s, long long nframes) {
+    // 1. an sc16 chunk at a C without an sc16 receiver: converted, then the fp32 forms
+    int rc = OFDM_OK;
+    if (s.f32) rc = ofdm_iq_convert_sc16(sc16_of(s), (long long)(nframes * p->frame_in), p->scale, s.f32, p->s_comp);
+    if (rc) return rc;
+    ofdm_cf32 *iq = s.f32 ? s.f32 : static_cast<ofdm_cf32 *>(s.iq);
+    // 2. the chunk's offsets from its cyclic prefixes, then the integer part in
+    // place on them; the derotating receiver takes them at C = 1024, at any
+    // other C the chunk (the pipeline's own memory) is derotated in place
+    const bool derotating = p->cfo && p->C == 1024;
+    if (p->cfo) {
+        rc = ofdm_frame_cfo_estimate(iq, nframes, p->S, p->R, p->C, p->cp, p->cp_skip, nullptr, s.eps, p->s_comp);
+        if (rc == OFDM_OK && p->search > 0)
+            rc = ofdm_frame_cfo_acquire(iq, nframes, p->S, p->R, p->C, p->cp, p->X, p->search, p->search_ratio, s.eps,
+                                        s.eps, nullptr, nullptr, p->s_comp);
+        if (rc == OFDM_OK && !derotating)
+            rc = ofdm_frame_cfo_derotate(iq, iq, nframes, p->S, p->R, p->C, p->cp, s.eps, p->s_comp);
+        if (rc) return rc;
+    }
+    // 3. the source
+    const Source src = p->sc16 && !s.f32 ? Source::Sc16 : derotating ? Source::Cfo : Source::Plain;
+    // 4. the receiver; with denoising, estimate -> denoise -> combine (the one-launch demod cannot take it in)
+    if (p->taps_post > 0) {
+        rc = estimate(src, *p, s, iq, nframes);
+        if (rc == OFDM_OK)
+            rc = ofdm_frame_estimate_denoise(s.ws, p->ws_bytes, nframes, p->S, p->R, p->C, p->taps_post, p->taps_pre,
+                                             p->s_comp);
+        if (rc == OFDM_OK) rc = combine(src, *p, s, iq, nframes);
+    } else {
+        rc = demod(src, *p, s, iq, nframes);
+    }
+    if (rc) return rc;
+    // 5. a tracker, in place on the output, against the estimate step 4 left in the slot's workspace;
+    // the timing tracker contains the phase tracker and runs in its place, not before it
+    if (p->timing_mod)
+        return ofdm_frame_timing_track(s.out, nframes, p->S, p->R, p->C, s.ws, p->ws_bytes, p->timing_mod, s.out,
+                                       nullptr, nullptr, p->s_comp);
+    if (p->phase_mod)
+        return ofdm_frame_phase_track(s.out, nframes, p->S, p->R, p->C, s.ws, p->ws_bytes, p->phase_mod, s.out, nullptr,
+                                      p->s_comp);
+    return OFDM_OK;
+}
+
+// what ofdm_pipeline_set_phase_track / _set_timing_track refuse
+int check_track(const char *fn, const ofdm_pipeline *p, int modulation) {
+    if (!p) return err(OFDM_E_ARG, fn, "null pipeline");
+    if (modulation != 0 && modulation != OFDM_MOD_QPSK && modulation != OFDM_MOD_QAM16 && modulation != OFDM_MOD_QAM64 &&
+        modulation != OFDM_MOD_QAM256)
+        return err(OFDM_E_ARG, fn, "modulation must be 0 (off), 2, 4, 6 or 8");
     return OFDM_OK;
 }
 
@@ -268,90 +357,7 @@ int ofdm_pipeline_submit(ofdm_pipeline *p, long long nframes, ofdm_cf32 *out) {
     rel.enqueued = true;
     PL_TRY(hipStreamWaitEvent(p->s_comp, s.in_done, 0), fn, "hipStreamWaitEvent");
     if (s.used) PL_TRY(hipStreamWaitEvent(p->s_comp, s.out_done, 0), fn, "hipStreamWaitEvent");
-    if (nframes > 0 && p->cfo) {
-        // the chunk's offsets from its cyclic prefixes, then the derotating
-        // receiver (C = 1024) or the slot derotated in place and the fp32 forms
-        // (the slot, or the converted chunk of an sc16 pipeline, is the
-        // pipeline's own memory)
-        ofdm_cf32 *iq = s.f32 ? s.f32 : static_cast<ofdm_cf32 *>(s.iq);
-        const bool fused = p->C == 1024;
-        int rc = OFDM_OK;
-        if (s.f32)
-            rc = ofdm_iq_convert_sc16(static_cast<const ofdm_sc16 *>(s.iq), (long long)(nframes * p->frame_in), p->scale,
-                                      s.f32, p->s_comp);
-        if (rc == OFDM_OK)
-            rc = ofdm_frame_cfo_estimate(iq, nframes, p->S, p->R, p->C, p->cp, p->cp_skip, nullptr, s.eps, p->s_comp);
-        if (rc == OFDM_OK && p->search > 0)  // the integer part, in place on the slot's offsets
-            rc = ofdm_frame_cfo_acquire(iq, nframes, p->S, p->R, p->C, p->cp, p->X, p->search, p->search_ratio, s.eps,
-                                        s.eps, nullptr, nullptr, p->s_comp);
-        if (rc == OFDM_OK && !fused)
-            rc = ofdm_frame_cfo_derotate(iq, iq, nframes, p->S, p->R, p->C, p->cp, s.eps, p->s_comp);
-        if (rc == OFDM_OK && p->taps_post > 0) {
-            rc = fused ? ofdm_frame_estimate_cfo(iq, nframes, p->S, p->R, p->C, p->cp, p->X, s.ws, p->ws_bytes, s.eps,
-                                                 p->s_comp)
-                       : ofdm_frame_estimate(iq, nframes, p->S, p->R, p->C, p->cp, p->X, s.ws, p->ws_bytes, p->s_comp);
-            if (rc == OFDM_OK)
-                rc = ofdm_frame_estimate_denoise(s.ws, p->ws_bytes, nframes, p->S, p->R, p->C, p->taps_post,
-                                                 p->taps_pre, p->s_comp);
-            if (rc == OFDM_OK)
-                rc = fused ? ofdm_frame_combine_cfo(iq, nframes, p->S, p->R, p->C, p->cp, s.ws, p->ws_bytes, s.out,
-                                                    s.eps, p->s_comp)
-                           : ofdm_frame_combine(iq, nframes, p->S, p->R, p->C, p->cp, s.ws, p->ws_bytes, s.out,
-                                                p->s_comp);
-        } else if (rc == OFDM_OK) {
-            rc = fused ? ofdm_frame_demod_cfo(iq, nframes, p->S, p->R, p->C, p->cp, p->X, s.ws, p->ws_bytes, s.out,
-                                              s.eps, p->s_comp)
-                       : ofdm_frame_demod(iq, nframes, p->S, p->R, p->C, p->cp, p->X, s.ws, p->ws_bytes, s.out,
-                                          p->s_comp);
-        }
-        if (rc) return rc;
-    } else if (nframes > 0 && p->taps_post > 0) {
-        // estimate -> denoise -> combine (the one-launch demod cannot take the denoising in)
-        const bool sc = p->sc16 && !s.f32;
-        const ofdm_cf32 *iq = static_cast<const ofdm_cf32 *>(s.f32 ? s.f32 : s.iq);
-        const ofdm_sc16 *iq16 = static_cast<const ofdm_sc16 *>(s.iq);
-        int rc = OFDM_OK;
-        if (s.f32) rc = ofdm_iq_convert_sc16(iq16, (long long)(nframes * p->frame_in), p->scale, s.f32, p->s_comp);
-        if (rc == OFDM_OK)
-            rc = sc ? ofdm_frame_estimate_sc16(iq16, nframes, p->S, p->R, p->C, p->cp, p->scale, p->X, s.ws,
-                                               p->ws_bytes, p->s_comp)
-                    : ofdm_frame_estimate(iq, nframes, p->S, p->R, p->C, p->cp, p->X, s.ws, p->ws_bytes, p->s_comp);
-        if (rc == OFDM_OK)
-            rc = ofdm_frame_estimate_denoise(s.ws, p->ws_bytes, nframes, p->S, p->R, p->C, p->taps_post, p->taps_pre,
-                                             p->s_comp);
-        if (rc == OFDM_OK)
-            rc = sc ? ofdm_frame_combine_sc16(iq16, nframes, p->S, p->R, p->C, p->cp, p->scale, s.ws, p->ws_bytes,
-                                              s.out, p->s_comp)
-                    : ofdm_frame_combine(iq, nframes, p->S, p->R, p->C, p->cp, s.ws, p->ws_bytes, s.out, p->s_comp);
-        if (rc) return rc;
-    } else if (nframes > 0) {
-        int rc;
-        if (!p->sc16) {
-            rc = ofdm_frame_demod(static_cast<const ofdm_cf32 *>(s.iq), nframes, p->S, p->R, p->C, p->cp, p->X, s.ws,
-                                  p->ws_bytes, s.out, p->s_comp);
-        } else if (!s.f32) {
-            rc = ofdm_frame_demod_sc16(static_cast<const ofdm_sc16 *>(s.iq), nframes, p->S, p->R, p->C, p->cp,
-                                       p->scale, p->X, s.ws, p->ws_bytes, s.out, p->s_comp);
-        } else {
-            rc = ofdm_iq_convert_sc16(static_cast<const ofdm_sc16 *>(s.iq), (long long)(nframes * p->frame_in),
-                                      p->scale, s.f32, p->s_comp);
-            if (rc == OFDM_OK)
-                rc = ofdm_frame_demod(s.f32, nframes, p->S, p->R, p->C, p->cp, p->X, s.ws, p->ws_bytes, s.out,
-                                      p->s_comp);
-        }
-        if (rc) return rc;
-    }
-    if (nframes > 0 && p->timing_mod) {
-        // contains the phase tracker: it runs in its place, not before it
-        int rc = ofdm_frame_timing_track(s.out, nframes, p->S, p->R, p->C, s.ws, p->ws_bytes, p->timing_mod, s.out,
-                                         nullptr, nullptr, p->s_comp);
-        if (rc) return rc;
-    } else if (nframes > 0 && p->phase_mod) {
-        // whichever receiver form ran above left its estimate in the slot's workspace
-        int rc = ofdm_frame_phase_track(s.out, nframes, p->S, p->R, p->C, s.ws, p->ws_bytes, p->phase_mod, s.out, nullptr,
-                                        p->s_comp);
-        if (rc) return rc;
-    }
+    if (int rc = nframes > 0 ? receive(p, s, nframes) : OFDM_OK) return rc;
     PL_TRY(hipEventRecord(s.comp_done, p->s_comp), fn, "hipEventRecord");
     PL_TRY(hipStreamWaitEvent(p->s_out, s.comp_done, 0), fn, "hipStreamWaitEvent");
     if (out && nframes > 0)
@@ -403,7 +409,7 @@ int ofdm_pipeline_set_cfo_search(ofdm_pipeline *p, int max_shift, float min_rati
     if (max_shift < 0 || max_shift > OFDM_ACQ_MAX_SHIFT)
         return err(OFDM_E_ARG, fn, "max_shift out of [0, OFDM_ACQ_MAX_SHIFT]");
     if (4 * max_shift > p->C) return err(OFDM_E_ARG, fn, "max_shift: the search needs 4 * max_shift <= C");
-    if (!(min_ratio >= 1.f && min_ratio <= 3.402823466e38f))
+    if (!(min_ratio >= 1.f && positive_finite(min_ratio)))
         return err(OFDM_E_ARG, fn, "min_ratio: the gate needs a finite ratio >= 1");
     if (max_shift > 0 && p->C < 8) return err(OFDM_E_UNSUPPORTED, fn, "the search covers C in [8, 8192]");
     p->search = max_shift;
@@ -412,21 +418,13 @@ int ofdm_pipeline_set_cfo_search(ofdm_pipeline *p, int max_shift, float min_rati
 }
 
 int ofdm_pipeline_set_phase_track(ofdm_pipeline *p, int modulation) {
-    static const char *fn = "ofdm_pipeline_set_phase_track";
-    if (!p) return err(OFDM_E_ARG, fn, "null pipeline");
-    if (modulation != 0 && modulation != OFDM_MOD_QPSK && modulation != OFDM_MOD_QAM16 && modulation != OFDM_MOD_QAM64 &&
-        modulation != OFDM_MOD_QAM256)
-        return err(OFDM_E_ARG, fn, "modulation must be 0 (off), 2, 4, 6 or 8");
+    if (int rc = check_track("ofdm_pipeline_set_phase_track", p, modulation)) return rc;
     p->phase_mod = modulation;
     return OFDM_OK;
 }
 
 int ofdm_pipeline_set_timing_track(ofdm_pipeline *p, int modulation) {
-    static const char *fn = "ofdm_pipeline_set_timing_track";
-    if (!p) return err(OFDM_E_ARG, fn, "null pipeline");
-    if (modulation != 0 && modulation != OFDM_MOD_QPSK && modulation != OFDM_MOD_QAM16 && modulation != OFDM_MOD_QAM64 &&
-        modulation != OFDM_MOD_QAM256)
-        return err(OFDM_E_ARG, fn, "modulation must be 0 (off), 2, 4, 6 or 8");
+    if (int rc = check_track("ofdm_pipeline_set_timing_track", p, modulation)) return rc;
     p->timing_mod = modulation;
     return OFDM_OK;
 }
