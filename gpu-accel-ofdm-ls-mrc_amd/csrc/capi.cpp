@@ -9,11 +9,14 @@
 #include <map>
 #include <mutex>
 #include <random>
+#include <set>
 #include <string>
+#include <vector>
 
 #include "../../include/ofdm_lsmrc.h"
 #include "../../include/ofdm_lsmrc_acquire.h"
 #include "../../include/ofdm_lsmrc_decode.h"
+#include "../../include/ofdm_lsmrc_ldpc.h"
 #include "../../include/ofdm_lsmrc_timing.h"
 #include "launch.hpp"
 
@@ -1180,6 +1183,153 @@ int ofdm_viterbi_decode(const void *d_llr, int llr_format, float llr_scale, long
     return hip_check(ofdm::launch_viterbi(d_llr, llr_format, llr_scale, cw_stride, ncw, L, T, n_rx, code->n_out, code->g,
                                           code->terminated, code->punct_period, code->punct_mask, d_bits, out_stride,
                                           d_metric, d_scratch, hs(stream)),
+                     fn);
+}
+
+// QC-LDPC decoder (include/ofdm_lsmrc_ldpc.h).  A handle is a host copy of the
+// base table in the kernel's form; g_ldpc lists the live ones, so a destroyed
+// handle is refused without being read.  d_tab is made by the first decode that
+// launches (ldpc_table), never by a refusal.
+}  // extern "C"
+
+struct ofdm_ldpc_code {
+    int mb, nb, Z, nnz;
+    std::vector<int> tab;  // row_ptr[mb + 1], then (shift << 16) | col * Z per entry
+    int *d_tab = nullptr;
+    int dev = -1;
+};
+
+namespace {
+std::mutex g_ldpc_mu;
+std::set<const ofdm_ldpc_code *> g_ldpc;
+
+bool ldpc_live(const ofdm_ldpc_code *c) {
+    std::lock_guard<std::mutex> lock(g_ldpc_mu);
+    return c && g_ldpc.count(c);
+}
+
+hipError_t ldpc_table(ofdm_ldpc_code *c) {
+    std::lock_guard<std::mutex> lock(g_ldpc_mu);
+    if (c->d_tab) return hipSuccess;
+    int *d = nullptr;
+    hipError_t e = hipGetDevice(&c->dev);
+    if (e != hipSuccess) return e;
+    const size_t bytes = c->tab.size() * sizeof(int);
+    if ((e = hipMalloc(reinterpret_cast<void **>(&d), bytes)) != hipSuccess) return e;
+    if ((e = hipMemcpy(d, c->tab.data(), bytes, hipMemcpyHostToDevice)) != hipSuccess) {
+        (void)hipFree(d);
+        return e;
+    }
+    c->d_tab = d;
+    return hipSuccess;
+}
+}  // namespace
+
+extern "C" {
+
+int ofdm_ldpc_code_create(const ofdm_qc_ldpc *code, ofdm_ldpc_code_t *handle) {
+    static const char *fn = "ofdm_ldpc_code_create";
+    if (!code) return fail(OFDM_E_ARG, "%s: null code", fn);
+    if (!handle) return fail(OFDM_E_ARG, "%s: null handle pointer", fn);
+    if (!code->row_ptr || !code->col || !code->shift) return fail(OFDM_E_ARG, "%s: null row_ptr, col or shift", fn);
+    const int mb = code->mb, nb = code->nb, Z = code->Z;
+    if (mb < 1) return fail(OFDM_E_ARG, "%s: mb=%d < 1", fn, mb);
+    if (nb <= mb) return fail(OFDM_E_ARG, "%s: nb=%d, needs nb > mb=%d", fn, nb, mb);
+    if (Z < 2) return fail(OFDM_E_ARG, "%s: Z=%d < 2", fn, Z);
+    if (code->row_ptr[0] != 0) return fail(OFDM_E_ARG, "%s: row_ptr[0]=%d, not 0", fn, code->row_ptr[0]);
+    int maxdeg = 0;
+    for (int r = 0; r < mb; ++r) {
+        const int e0 = code->row_ptr[r], e1 = code->row_ptr[r + 1];
+        if ((long long)e1 - e0 < 2) return fail(OFDM_E_ARG, "%s: row %d has degree %lld, below 2", fn, r, (long long)e1 - e0);
+        if (e1 - e0 > maxdeg) maxdeg = e1 - e0;
+        for (int e = e0; e < e1; ++e) {
+            const int c = code->col[e], sh = code->shift[e];
+            if (c < 0 || c >= nb) return fail(OFDM_E_ARG, "%s: row %d: col=%d outside 0..%d", fn, r, c, nb - 1);
+            if (e > e0 && c <= code->col[e - 1])
+                return fail(OFDM_E_ARG, "%s: row %d: col=%d not above its predecessor %d", fn, r, c, code->col[e - 1]);
+            if (sh < 0 || sh >= Z) return fail(OFDM_E_ARG, "%s: row %d: shift=%d outside 0..%d", fn, r, sh, Z - 1);
+        }
+    }
+    if (Z > 384) return fail(OFDM_E_UNSUPPORTED, "%s: Z=%d above 384", fn, Z);
+    if (maxdeg > 32) return fail(OFDM_E_UNSUPPORTED, "%s: a row of degree %d, above 32", fn, maxdeg);
+    if ((long long)nb * Z > 32768) return fail(OFDM_E_UNSUPPORTED, "%s: N=%lld above 32768", fn, (long long)nb * Z);
+    ofdm_ldpc_code *c = new ofdm_ldpc_code;
+    c->mb = mb, c->nb = nb, c->Z = Z, c->nnz = code->row_ptr[mb];
+    c->tab.assign(code->row_ptr, code->row_ptr + mb + 1);
+    for (int e = 0; e < c->nnz; ++e) c->tab.push_back((int)(((unsigned)code->shift[e] << 16) | (unsigned)(code->col[e] * Z)));
+    {
+        std::lock_guard<std::mutex> lock(g_ldpc_mu);
+        g_ldpc.insert(c);
+    }
+    *handle = c;
+    return OFDM_OK;
+}
+
+int ofdm_ldpc_code_destroy(ofdm_ldpc_code_t handle) {
+    {
+        std::lock_guard<std::mutex> lock(g_ldpc_mu);
+        if (!handle || !g_ldpc.erase(handle)) return fail(OFDM_E_ARG, "ofdm_ldpc_code_destroy: null or destroyed handle");
+    }
+    if (handle->d_tab) (void)hipFree(handle->d_tab);
+    delete handle;
+    return OFDM_OK;
+}
+
+int ofdm_ldpc_workspace_bytes(ofdm_ldpc_code_t code, long long ncw, size_t *bytes) {
+    static const char *fn = "ofdm_ldpc_workspace_bytes";
+    if (!ldpc_live(code)) return fail(OFDM_E_ARG, "%s: null or destroyed handle", fn);
+    if (ncw < 0) return fail(OFDM_E_ARG, "%s: ncw=%lld", fn, ncw);
+    if (!bytes) return fail(OFDM_E_ARG, "%s: null bytes", fn);
+    *bytes = ofdm::ldpc_scratch_bytes(code->nb * code->Z, code->Z, code->nnz, ncw);
+    return OFDM_OK;
+}
+
+int ofdm_ldpc_decode(const void *d_llr, int llr_format, float llr_scale, long long cw_stride, long long ncw,
+                     ofdm_ldpc_code_t code, int pos0, int n_rx, int max_iter, int norm16, int offset, int early_stop,
+                     int n_bits, unsigned char *d_bits, long long out_stride, int *d_iters, void *d_scratch,
+                     size_t scratch_bytes, ofdm_stream_t stream) {
+    static const char *fn = "ofdm_ldpc_decode";
+    if (!ldpc_live(code)) return fail(OFDM_E_ARG, "%s: null or destroyed handle", fn);
+    const int N = code->nb * code->Z;
+    if (llr_format != OFDM_LLR_F32 && llr_format != OFDM_LLR_I8)
+        return fail(OFDM_E_ARG, "%s: llr_format=%d (OFDM_LLR_F32 0 or OFDM_LLR_I8 1)", fn, llr_format);
+    if (llr_format == OFDM_LLR_F32 && !positive_finite(llr_scale))
+        return fail(OFDM_E_ARG, "%s: llr_scale=%g, OFDM_LLR_F32 needs a positive finite scale", fn, (double)llr_scale);
+    if (pos0 < 0 || n_rx < 1 || (long long)pos0 + n_rx > N)
+        return fail(OFDM_E_ARG, "%s: window pos0=%d n_rx=%d outside the codeword's N=%d positions", fn, pos0, n_rx, N);
+    if (cw_stride < n_rx) return fail(OFDM_E_ARG, "%s: cw_stride=%lld below n_rx=%d", fn, cw_stride, n_rx);
+    if (n_bits < 1 || n_bits > N) return fail(OFDM_E_ARG, "%s: n_bits=%d outside 1..N=%d", fn, n_bits, N);
+    const long long nbytes = (n_bits + 7) / 8;
+    if (out_stride < nbytes)
+        return fail(OFDM_E_ARG, "%s: out_stride=%lld below ceil(n_bits/8)=%lld", fn, out_stride, nbytes);
+    if (max_iter < 1 || max_iter > 1000) return fail(OFDM_E_ARG, "%s: max_iter=%d outside 1..1000", fn, max_iter);
+    if (norm16 < 1 || norm16 > 16) return fail(OFDM_E_ARG, "%s: norm16=%d outside 1..16", fn, norm16);
+    if (offset < 0 || offset > 127) return fail(OFDM_E_ARG, "%s: offset=%d outside 0..127", fn, offset);
+    if (early_stop != 0 && early_stop != 1) return fail(OFDM_E_ARG, "%s: early_stop=%d (0 or 1)", fn, early_stop);
+    if (ncw < 0) return fail(OFDM_E_ARG, "%s: ncw=%lld", fn, ncw);
+    if (ncw == 0) return OFDM_OK;
+    if (!d_llr) return fail(OFDM_E_ARG, "%s: null d_llr", fn);
+    if (!d_bits) return fail(OFDM_E_ARG, "%s: null d_bits", fn);
+    const size_t need = ofdm::ldpc_scratch_bytes(N, code->Z, code->nnz, ncw);
+    if (scratch_bytes < need)
+        return fail(OFDM_E_ARG, "%s: scratch_bytes=%zu below ofdm_ldpc_workspace_bytes=%zu", fn, scratch_bytes, need);
+    if (need && !d_scratch) return fail(OFDM_E_ARG, "%s: null d_scratch", fn);
+    const size_t esz = llr_format == OFDM_LLR_F32 ? 4 : 1;
+    if (!aligned(d_llr, esz)) return fail(OFDM_E_ARG, "%s: d_llr must be 4-byte aligned for OFDM_LLR_F32", fn);
+    if (!aligned(d_iters, 4)) return fail(OFDM_E_ARG, "%s: d_iters must be 4-byte aligned", fn);
+    const uintptr_t lb = (uintptr_t)((ncw - 1) * cw_stride + n_rx) * esz;  // the LLR range, gaps included
+    const uintptr_t bb = (uintptr_t)((ncw - 1) * out_stride + nbytes);     // d_bits likewise
+    const uintptr_t ib = d_iters ? (uintptr_t)ncw * sizeof(int) : 0, sb = d_scratch ? need : 0;
+    if (overlaps(d_bits, bb, d_llr, lb)) return fail(OFDM_E_ARG, "%s: d_bits overlaps d_llr", fn);
+    if (ib && (overlaps(d_iters, ib, d_llr, lb) || overlaps(d_iters, ib, d_bits, bb)))
+        return fail(OFDM_E_ARG, "%s: d_iters overlaps d_llr or d_bits", fn);
+    if (sb && (overlaps(d_scratch, sb, d_llr, lb) || overlaps(d_scratch, sb, d_bits, bb) ||
+               (ib && overlaps(d_scratch, sb, d_iters, ib))))
+        return fail(OFDM_E_ARG, "%s: d_scratch overlaps d_llr, d_bits or d_iters", fn);
+    if (hipError_t e = ldpc_table(code)) return hip_check(e, "ofdm_ldpc_decode (base table)");
+    return hip_check(ofdm::launch_ldpc(d_llr, llr_format, llr_scale, cw_stride, ncw, code->d_tab, code->mb, N, code->Z,
+                                       code->nnz, pos0, n_rx, max_iter, norm16, offset, early_stop, n_bits, d_bits,
+                                       out_stride, d_iters, d_scratch, hs(stream)),
                      fn);
 }
 

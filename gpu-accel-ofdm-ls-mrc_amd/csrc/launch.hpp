@@ -257,6 +257,31 @@ hipError_t launch_viterbi(const void *llr, int fmt, float llr_scale, long long c
                           long long n_rx, int n_out, const int *g, int terminated, int p, unsigned mask,
                           unsigned char *bits, long long out_stride, int *metric, void *scratch, hipStream_t s);
 
+// Layered min-sum decoder for quasi-cyclic LDPC codes (ldpc.hip states the
+// kernel, include/ofdm_lsmrc_ldpc.h the definition).  d_tab: the base table on
+// the device, row_ptr[mb + 1] then one word per entry, (shift << 16) | col * Z;
+// N = nb * Z; llr, bits as the Viterbi decoder's, the window (pos0, n_rx);
+// iters [ncw] (may be null); scratch: ldpc_scratch_bytes(...) bytes (null
+// where that is 0).  ldpc_plan: a codeword's L and messages stay in LDS while
+// they fit LDPC_LDS_BYTES, G codewords to a workgroup of one wave while
+// G * Z <= 64; beyond, the messages take a scratch slot per workgroup.
+constexpr int LDPC_LDS_BYTES = 65536;     // 2 N + nnz * Z up to here: messages in LDS
+constexpr int LDPC_ROUND_LDS = 16384;     // workgroups of a launch, each taking codeword groups in turn: messages in LDS ...
+constexpr int LDPC_ROUND_SCRATCH = 1024;  // ... and in scratch (one nnz * Z-byte slot each)
+struct LdpcPlan {
+    bool msg_lds;  // messages in LDS
+    int G;         // codewords per workgroup
+    int threads;   // of a workgroup: G * Z rounded up to whole waves
+    size_t lds;    // dynamic LDS bytes
+    size_t slot;   // scratch bytes per workgroup
+};
+LdpcPlan ldpc_plan(int N, int Z, int nnz);
+size_t ldpc_scratch_bytes(int N, int Z, int nnz, long long ncw);
+hipError_t launch_ldpc(const void *llr, int fmt, float llr_scale, long long cw_stride, long long ncw, const int *d_tab,
+                       int mb, int N, int Z, int nnz, int pos0, int n_rx, int max_iter, int norm16, int offset,
+                       int early_stop, int n_bits, unsigned char *bits, long long out_stride, int *iters, void *scratch,
+                       hipStream_t s);
+
 // OFDM modulator (tx_mod.hip; any C but 1024: fft_any.hip k_tx_any): row i =
 // X + i*ldx (K values, through the bin placement `map`) -> backward FFT ->
 // iq + i*(C+cp): the last cp samples, then the C samples, times 1/peak

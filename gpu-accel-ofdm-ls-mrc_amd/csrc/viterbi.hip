@@ -53,6 +53,7 @@
 //           ballot, find-first); metric: that state's path metric.
 // No atomics, no private segment.
 #include "launch.hpp"
+#include "llr_quant.hpp"
 
 namespace ofdm {
 namespace vit {
@@ -65,22 +66,9 @@ constexpr int NEG = -(1 << 30);
 // it does for the readlane builtin (an asm statement would get neither).
 extern "C" __device__ int ofdm_vit_writelane(int value, int lane, int old) __asm("llvm.amdgcn.writelane.i32");
 
-// One LLR element of the codeword at element e0, as loaded: the float's bits or
-// the sign-extended byte; x: its index in the codeword's stream, 0 at and
-// beyond n_rx (never read).  quant() makes the integer q of the definition
-// from it; the two are apart so that a load stays in flight until its
-// register is needed.
-__device__ __forceinline__ int load_raw(const void *llr, int fmt, long long e0, int x, int n_rx) {
-    if (x >= n_rx) return 0;
-    if (fmt == 1) return static_cast<const signed char *>(llr)[e0 + x];
-    return __float_as_int(static_cast<const float *>(llr)[e0 + x]);
-}
-__device__ __forceinline__ int quant(int raw, int fmt, float scale) {
-    if (fmt == 1) return raw < -127 ? -127 : raw;
-    const float f = __int_as_float(raw) * scale;
-    const float v = f == f ? __builtin_fminf(__builtin_fmaxf(f, -127.f), 127.f) : 0.f;  // soft_demap.hip quant8
-    return (int)__builtin_rintf(v);
-}
+// One LLR element as loaded and its integer q in [-127, 127]: shared with ldpc.hip.
+using llrq::load_raw;
+using llrq::quant;
 
 // One add-compare-select step on the wave's 64 metrics; step t's decision
 // word goes to lane `sel` of (dlo, dhi).

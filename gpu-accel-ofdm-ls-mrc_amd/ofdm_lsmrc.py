@@ -27,6 +27,7 @@ HEADER_PATH = os.path.join(os.path.dirname(HERE), "include", "ofdm_lsmrc.h")
 ACQUIRE_HEADER_PATH = os.path.join(os.path.dirname(HERE), "include", "ofdm_lsmrc_acquire.h")
 TIMING_HEADER_PATH = os.path.join(os.path.dirname(HERE), "include", "ofdm_lsmrc_timing.h")
 DECODE_HEADER_PATH = os.path.join(os.path.dirname(HERE), "include", "ofdm_lsmrc_decode.h")
+LDPC_HEADER_PATH = os.path.join(os.path.dirname(HERE), "include", "ofdm_lsmrc_ldpc.h")
 
 _c = ctypes
 _P = _c.c_void_p
@@ -129,10 +130,19 @@ _SIGS_DECODE = {
     "ofdm_viterbi_decode": (_I, [_P, _I, _c.c_float, _LL, _LL, _I, _P, _P, _LL, _P, _P, _c.c_size_t, _P]),
 }
 
+# include/ofdm_lsmrc_ldpc.h (likewise)
+_SIGS_LDPC = {
+    "ofdm_ldpc_code_create": (_I, [_P, _c.POINTER(_P)]),
+    "ofdm_ldpc_code_destroy": (_I, [_P]),
+    "ofdm_ldpc_workspace_bytes": (_I, [_P, _LL, _c.POINTER(_c.c_size_t)]),
+    "ofdm_ldpc_decode": (_I, [_P, _I, _c.c_float, _LL, _LL, _P, _I, _I, _I, _I, _I, _I, _I, _P, _LL, _P, _P,
+                              _c.c_size_t, _P]),
+}
+
 
 def _all_sigs():
     return (list(_SIGS.items()) + list(_SIGS_ACQUIRE.items()) + list(_SIGS_TIMING.items())
-            + list(_SIGS_DECODE.items()))
+            + list(_SIGS_DECODE.items()) + list(_SIGS_LDPC.items()))
 
 _lib = None
 
@@ -141,7 +151,8 @@ def build_id():
     """Identity of the product library's build: the first 16 hex digits of
     a SHA-256 over its sources (csrc/, the Makefile, include/ofdm_lsmrc.h,
     include/ofdm_lsmrc_acquire.h, include/ofdm_lsmrc_timing.h,
-    include/ofdm_lsmrc_decode.h), in sorted order.  PMC profiles record it
+    include/ofdm_lsmrc_decode.h, include/ofdm_lsmrc_ldpc.h), in sorted order.
+    PMC profiles record it
     (scripts/pmc_summary.py) and bench.py attaches a profile's traffic only to
     the build it measured."""
     import hashlib
@@ -149,7 +160,7 @@ def build_id():
     csrc = os.path.join(HERE, "csrc")
     files = [os.path.join(csrc, f) for f in sorted(os.listdir(csrc))] + [os.path.join(HERE, "Makefile"), HEADER_PATH,
                                                                          ACQUIRE_HEADER_PATH, TIMING_HEADER_PATH,
-                                                                         DECODE_HEADER_PATH]
+                                                                         DECODE_HEADER_PATH, LDPC_HEADER_PATH]
     for f in files:
         if os.path.isfile(f):
             h.update(os.path.basename(f).encode() + b"\0")
@@ -867,6 +878,107 @@ def viterbi_decode(llr, code, L, ncw=None, stride=None, scale=1.0, out=None, out
                                      _dptr(ws, "ws") if ws is not None and ws.numel() else None,
                                      ws.numel() if ws is not None else 0, _stream(stream)), "ofdm_viterbi_decode")
     return out, metric
+
+
+class QcLdpcDesc(_c.Structure):
+    """ofdm_qc_ldpc (include/ofdm_lsmrc_ldpc.h): the base matrix as the C entry takes it."""
+    _fields_ = [("mb", _I), ("nb", _I), ("Z", _I), ("row_ptr", _c.POINTER(_I)), ("col", _c.POINTER(_I)),
+                ("shift", _c.POINTER(_I))]
+
+
+class QcLdpc:
+    """A quasi-cyclic LDPC code and the owner of its ofdm_ldpc_code_t handle.
+    rows: one list per base row of (column, shift) pairs, columns strictly
+    increasing; entry (c, s) of row r connects check r Z + i to variable
+    c Z + (i + s) mod Z.  The handle is destroyed with the object (close())."""
+
+    def __init__(self, mb, nb, Z, rows):
+        rows = [list(r) for r in rows]
+        if len(rows) != mb:
+            raise OfdmError(f"{len(rows)} rows given for mb={mb}")
+        self.mb, self.nb, self.Z, self.rows = mb, nb, Z, rows
+        self.N, self.M = nb * Z, mb * Z
+        ptr = [0]
+        for r in rows:
+            ptr.append(ptr[-1] + len(r))
+        self.nnz = ptr[-1]
+        self._arrays = ((_I * (mb + 1))(*ptr), (_I * max(self.nnz, 1))(*[c for r in rows for c, _ in r]),
+                        (_I * max(self.nnz, 1))(*[s for r in rows for _, s in r]))
+        self.desc = QcLdpcDesc(mb, nb, Z, *[_c.cast(a, _c.POINTER(_I)) for a in self._arrays])
+        self.handle = _P(None)
+        _check(lib().ofdm_ldpc_code_create(_c.byref(self.desc), _c.byref(self.handle)), "ofdm_ldpc_code_create")
+
+    def close(self):
+        if self.handle is not None and self.handle.value:
+            lib().ofdm_ldpc_code_destroy(self.handle)
+            self.handle = _P(None)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def ldpc_workspace_bytes(code, ncw):
+    n = _c.c_size_t(0)
+    _check(lib().ofdm_ldpc_workspace_bytes(code.handle, ncw, _c.byref(n)), "ofdm_ldpc_workspace_bytes")
+    return n.value
+
+
+def ldpc_decode(llr, code, ncw=None, stride=None, scale=1.0, pos0=0, n_rx=None, max_iter=20, norm16=12, offset=0,
+                early_stop=True, n_bits=None, out=None, out_stride=None, iters=None, ws=None, stream=None):
+    """Layered min-sum decoding of ncw codewords of the QcLdpc `code`
+    (include/ofdm_lsmrc_ldpc.h) -> (bits uint8 [ncw, out_stride], packed, bit t
+    of a codeword in bit t & 7 of byte t >> 3; iters int32 [ncw], +k: zero
+    syndrome after k iterations, -k: not).  llr: a device tensor, int8
+    (OFDM_LLR_I8) or float32 (OFDM_LLR_F32, quantised with `scale`); 2-D
+    (ncw, stride), or flat with ncw and stride (default: n_rx) given: codeword
+    c begins at element c * stride and holds positions pos0 .. pos0 + n_rx - 1
+    (n_rx defaults to the rest of the codeword, or to a 2-D llr's row where that
+    is shorter).  n_bits defaults to N.  ws: a byte tensor of
+    ldpc_workspace_bytes (made here if absent and needed)."""
+    import torch
+    if not isinstance(llr, torch.Tensor) or llr.dtype not in (torch.int8, torch.float32):
+        raise OfdmError("llr must be a torch.int8 or torch.float32 device tensor")
+    two_d = llr.dim() == 2 and ncw is None and stride is None
+    if two_d:
+        ncw, stride = llr.shape
+    if n_rx is None:
+        n_rx = code.N - pos0
+        if two_d:
+            n_rx = min(n_rx, stride)
+    if stride is None:
+        stride = n_rx
+    if ncw is None:
+        ncw = 0 if llr.numel() < n_rx else (llr.numel() - n_rx) // stride + 1
+    if ncw > 0 and llr.numel() < (ncw - 1) * stride + n_rx:
+        raise OfdmError(f"llr holds {llr.numel()} elements, {ncw} codewords at stride {stride} need "
+                        f"{(ncw - 1) * stride + n_rx}")
+    if n_bits is None:
+        n_bits = code.N
+    nbytes = (n_bits + 7) // 8
+    if out_stride is None:
+        out_stride = out.shape[-1] if out is not None and out.dim() == 2 else nbytes
+    if out is None:
+        out = torch.empty((ncw, out_stride), dtype=torch.uint8, device=llr.device)
+    elif out.dtype != torch.uint8 or (ncw > 0 and out.numel() < (ncw - 1) * out_stride + min(nbytes, out_stride)):
+        raise OfdmError(f"out must be a torch.uint8 tensor of {ncw} rows of {out_stride} bytes")
+    if iters is None:
+        iters = torch.empty(ncw, dtype=torch.int32, device=llr.device)
+    elif iters.dtype != torch.int32 or iters.numel() < ncw:
+        raise OfdmError(f"iters must be a torch.int32 tensor of {ncw} elements")
+    need = ldpc_workspace_bytes(code, ncw)
+    if ws is None and need:
+        ws = torch.empty(need, dtype=torch.uint8, device=llr.device)
+    live = ncw > 0
+    _check(lib().ofdm_ldpc_decode(_dptr(llr, "llr") if live else None, 1 if llr.dtype == torch.int8 else 0, scale, stride,
+                                  ncw, code.handle, pos0, n_rx, max_iter, norm16, offset, int(bool(early_stop)), n_bits,
+                                  _dptr(out, "out") if live else None, out_stride,
+                                  _dptr(iters, "iters") if live else None,
+                                  _dptr(ws, "ws") if ws is not None and ws.numel() else None,
+                                  ws.numel() if ws is not None else 0, _stream(stream)), "ofdm_ldpc_decode")
+    return out, iters
 
 
 def synth_frames(F, S, R, C, X, prefix=0, seed=1234, frame0=0, noise_std=0.01,
